@@ -4,7 +4,16 @@ Workload (BASELINE.json configs[1], "config #2"): a synthetic ~10 GB coordinate-
 paired-end BAM per GPU (tools/gen_bam.cpp, zlib level 5, htsjdk-style packing), read exactly as
 BAMRecordReader reads a FileVirtualSplit: BGZF scan, inflate, record-boundary walk, fixed-field
 + key decode, columnar pools.  A "step" = one hbam_decode_split over the rank's split with the
-compressed bytes resident in HBM.
+compressed bytes resident in HBM.  The file is the header blocks, BODY_COPIES copies of one
+generated body of size / BODY_COPIES bytes (whole generator segments, so every copy starts and
+ends on a BGZF block and a record boundary, as tools/config4.py builds its file), the body's
+unplaced tail and the EOF block: every launch has the 10 GB file's shape and statistics while
+the generator runs for a sixteenth of it.
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the
+line; `--dump-outputs DIR` also writes what the last timed step computed (a seeded sample) as
+DIR/<name>.npy.  Everything else -- the check of every record against the oracle, the random
+split parity, the CPU baseline, the Sort leg at N > 1, config #4 -- runs only with `--full`.
 
 N GPUs (torch.distributed, one rank per GPU, config #4's shape): the N ranks shard ONE file of
 N x ~10 GB by byte range.  Rank r holds file bytes [off_r, off_r + S_r) (its Hadoop FileSplit)
@@ -17,9 +26,10 @@ check subtracts them.
 
 Prints ONE JSON line (rank 0).  roofline = the dominant kernel (the Huffman pass: k_inflate_tokens
 at this size, k_inflate_wave for calls of up to HBAM_WAVE_MAX_BLOCKS blocks) with HIP events on
-the context's stream, plus per-stage and whole-pipeline fractions; cpu_baseline = the
-oracle's C restatement on a bounded sample on the host cores; parity = random FileVirtualSplits
-of the benchmarked file re-read by the oracle outside the timed region.
+the context's stream, plus per-stage and whole-pipeline fractions (the timed steps' own events,
+no further run).  With --full: cpu_baseline = the oracle's C restatement on a bounded sample on
+the host cores; parity = random FileVirtualSplits of the benchmarked file re-read by the oracle
+outside the timed region.
 """
 import argparse
 import ctypes as C
@@ -63,30 +73,128 @@ def cpu_model():
     return "unknown"
 
 
+BODY_COPIES = 16  # a rank's range = this many copies of one generated body
+
+
 def make_shard(size, seed, rank, world, threads, dist, dev):
-    """Rank's byte range of ONE file of world * m segments (+ the next rank's first segment).
-    Returns (host bytes, own length, file offset, file length, records in own range)."""
+    """Rank's byte range of ONE file: the header blocks (rank 0), world * BODY_COPIES copies of a
+    body of mb generator segments (BODY_COPIES per rank), the body's unplaced tail and the EOF
+    block (last rank); plus the next rank's first segment.  Returns (the range's pieces in file
+    order as host arrays, a repeated body being the same object each time; own length, file
+    offset, file length, records in own range)."""
     import genbam
     import torch
     t = time.time()
     probe = genbam.generate_range(1, 0, 1, seed=seed, threads=threads)
     m = max(1, int(round(size / len(probe))))
-    total = world * m
-    own = genbam.generate_range(total, rank * m, m, header=(rank == 0), tail=(rank == world - 1),
-                                seed=seed, threads=threads)
-    nxt = (genbam.generate_range(total, (rank + 1) * m, 1, seed=seed, threads=threads)
-           if rank < world - 1 else np.zeros(0, np.uint8))
-    sizes = [len(own)]
+    copies = min(BODY_COPIES, m)
+    mb = max(1, int(round(m / copies)))
+    body = probe if mb == 1 else genbam.generate_range(mb, 0, mb, seed=seed, threads=threads)
+    n_own = copies * int(body.n_records)
+    pieces = [np.asarray(body)] * copies
+    if rank == 0:
+        pieces.insert(0, np.asarray(genbam.generate_range(mb, 0, 0, header=True, seed=seed, threads=threads)))
+    if rank == world - 1:
+        tail = genbam.generate_range(mb, mb, 0, tail=True, seed=seed, threads=threads)
+        n_own += int(tail.n_records)
+        pieces.append(np.asarray(tail))
+    own_len = sum(len(p) for p in pieces)
+    if rank < world - 1:
+        pieces.append(np.asarray(probe))  # the next rank's first segment = the body's first
+    sizes = [own_len]
     if dist:
-        st = torch.tensor([len(own)], dtype=torch.int64, device=dev)
+        st = torch.tensor([own_len], dtype=torch.int64, device=dev)
         allv = [torch.zeros_like(st) for _ in range(world)]
         dist.all_gather(allv, st)
         sizes = [int(x.item()) for x in allv]
     off = sum(sizes[:rank])
-    buf = np.concatenate([np.asarray(own), nxt]) if len(nxt) else np.asarray(own)
-    log("rank %d: %d segments of %d, bytes [%d, %d) of a %.2f GB file, generated in %.1fs"
-        % (rank, m, total, off, off + len(own), sum(sizes) / 1e9, time.time() - t))
-    return buf, len(own), off, sum(sizes), int(own.n_records)
+    log("rank %d: %d copies of a body of %d segments, bytes [%d, %d) of a %.2f GB file, generated in %.1fs"
+        % (rank, copies, mb, off, off + own_len, sum(sizes) / 1e9, time.time() - t))
+    return pieces, own_len, off, sum(sizes), n_own
+
+
+def upload_pieces(pieces, dev):
+    """The pieces laid end to end in one device buffer (+ the 64 readable bytes libhbam wants
+    after the last): each distinct piece crosses to the device once, its repeats are copied there."""
+    import torch
+    n = sum(len(p) for p in pieces)
+    d = torch.empty(n + 64, dtype=torch.uint8, device=dev)
+    d[n:].zero_()
+    at, first = 0, {}
+    for p in pieces:
+        if id(p) in first:
+            d[at:at + len(p)].copy_(d[first[id(p)]:first[id(p)] + len(p)])
+        else:
+            d[at:at + len(p)].copy_(torch.from_numpy(p), non_blocking=False)
+            first[id(p)] = at
+        at += len(p)
+    torch.cuda.synchronize()
+    return d, n
+
+
+DUMP_RUNS, DUMP_RUN_LEN, DUMP_SEED, DUMP_BUDGET = 48, 256, 12345, 56e6
+
+
+def dump_outputs(ctx, cols, pool_bytes, out_dir):
+    """--dump-outputs: what the last timed step handed its caller (the device hbam_columns), as
+    DIR/<name>.npy.  The whole output is several times the file, so this writes the records of
+    DUMP_RUNS seeded runs of DUMP_RUN_LEN consecutive records (fewer when records are long: at most
+    DUMP_BUDGET bytes in all): `records` = their indices, each fixed column, the four offset
+    columns, and the runs' bytes of ubuf and of every pool, concatenated in run order; `totals` =
+    n_records, status, ubuf_len and each pool's length.  float64 where a value needs more than
+    24 bits (the int64 key as its high and low 32-bit halves), float32 otherwise: all exact."""
+    from hadoop_bam import _lib
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(cols.n_records)
+    ptr = lambda name: C.cast(getattr(cols, name), C.c_void_p).value
+
+    def get(name, dt, i0, cnt):
+        sz = np.dtype(dt).itemsize
+        return ctx.download(ptr(name) + i0 * sz, cnt * sz, dt).copy() if cnt else np.zeros(0, dt)
+    per_rec = 4.0 * (int(cols.ubuf_len) + pool_bytes) / max(n, 1) + 8 * (len(_lib.FIXED) + 6)
+    want = max(1, min(DUMP_RUNS * DUMP_RUN_LEN, int(DUMP_BUDGET / per_rec)))
+    if n <= want:
+        runs = [(0, n)]
+    else:
+        k = max(1, want // DUMP_RUN_LEN)
+        ln = min(DUMP_RUN_LEN, want)
+        rng = np.random.default_rng(DUMP_SEED)
+        # one run in each of k equal stretches of the records, so runs never overlap
+        runs = [(int(j * (n // k) + rng.integers(0, n // k - ln + 1)), ln) for j in range(k)]
+    out = {"records": np.concatenate([np.arange(i0, i0 + c) for i0, c in runs]).astype(np.float64)}
+    fixed = {name: np.concatenate([get(name, dt, i0, c) for i0, c in runs]) for name, dt in _lib.FIXED}
+    for name, a in fixed.items():
+        if name == "key":
+            out["key_hi"] = (a >> 32).astype(np.float64)
+            out["key_lo"] = (a & 0xffffffff).astype(np.float64)
+        else:
+            out[name] = a.astype(np.float64 if a.itemsize > 2 else np.float32)
+    lens = {}
+    for pool, dt, offn in (("names", np.uint8, "name_off"), ("cigars", np.uint32, "cigar_off"),
+                           ("seq", np.uint8, "seq_off"), ("qual", np.uint8, "seq_off"),
+                           ("aux", np.uint8, "aux_off")):
+        offs = [get(offn, np.uint64, i0, c + 1) for i0, c in runs]
+        out[offn] = np.concatenate(offs).astype(np.float64)  # c + 1 offsets per run
+        parts = [get(pool, dt, int(o[0]), int(o[-1] - o[0])) for o in offs]
+        out[pool] = np.concatenate(parts).astype(np.float64 if dt is np.uint32 else np.float32)
+        lens[pool] = int(get(offn, np.uint64, n, 1)[0]) if n else 0
+    parts, at = [], 0
+    for i0, c in runs:
+        if c:
+            beg = int(fixed["rec_off"][at])
+            end = int(fixed["rec_off"][at + c - 1]) + 4 + int(fixed["block_size"][at + c - 1])
+            parts.append(get("ubuf", np.uint8, beg, end - beg))
+        at += c
+    out["ubuf"] = (np.concatenate(parts) if parts else np.zeros(0, np.uint8)).astype(np.float32)
+    out["totals"] = np.array([n, int(cols.status), int(cols.ubuf_len)] +
+                             [lens[k] for k in ("names", "cigars", "seq", "qual", "aux")], np.float64)
+    total = 0
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= 64e6, total
+    log("dump: %d records in %d runs, %d arrays, %.1f MB -> %s" % (len(out["records"]), len(runs), len(out),
+                                                                  total / 1e6, out_dir))
 
 
 def cpu_baseline(data, budget_s, threads):
@@ -168,7 +276,7 @@ def parity_at_size(ctx, buf, dbuf, n_splits, seed, threads, whole=None):
     assert rc == 0
     sub = np.ascontiguousarray(buf)
     mism, recs = 0, 0
-    w_recs, w_max, w_mism = 0, 0, 0
+    w_recs, w_max, w_mism, w_false = 0, 0, 0, 0
     res = [None] * n_splits
 
     def ref_one(i):
@@ -207,6 +315,13 @@ def parity_at_size(ctx, buf, dbuf, n_splits, seed, threads, whole=None):
         mism += 0 if same else 1
         if whole is not None and same and d["n"]:
             lo = int(np.searchsorted(whole["voffset"], d["voffset"][0]))
+            if lo >= whole["n"] or int(whole["voffset"][lo]) != int(d["voffset"][0]):
+                # the guess (device == oracle, checked above) is no record start of the file: the
+                # guesser's heuristics (BAMSplitGuesser.java:155-209) can accept a position one byte
+                # before a record whose refIDs are 0 (every field shifted by a byte still passes),
+                # and what a reader decodes from there are not the file's records
+                w_false += 1
+                continue
             ok = lo + d["n"] <= whole["n"] and same_records(whole, lo, d, 0, d["n"])
             w_recs += d["n"]
             w_max = max(w_max, lo + d["n"])
@@ -217,6 +332,7 @@ def parity_at_size(ctx, buf, dbuf, n_splits, seed, threads, whole=None):
     if whole is not None:
         out["whole_shard"] = {"records_checked": w_recs, "highest_record_index": w_max,
                               "shard_records": whole["n"], "mismatches": w_mism,
+                              "splits_guessed_off_a_record_start": w_false,
                               "what": "the same records inside the timed whole-shard decode "
                                       "(one launch per kernel) equal the verified split decodes"}
     return out
@@ -319,6 +435,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--size", type=float, default=10e9, help="compressed bytes per GPU")
     ap.add_argument("--seed", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (a seeded sample of its "
+                         "columns and pools, see dump_outputs) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: every record of the timed launch and random "
+                         "splits against the oracle, the CPU baseline, the Sort leg (N > 1); needed for --config4. "
+                         "The options below only refine a --full run")
     ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of oracle baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--parity-splits", type=int, default=32)
@@ -340,6 +463,10 @@ def main():
     ap.add_argument("--c4-body", type=float, default=5e9, help="config #4: generated body repeated to fill the file")
     ap.add_argument("--c4-window", type=float, default=0, help="config #4: window bytes (0: from free HBM)")
     args = ap.parse_args()
+    if args.config4 and not args.full:
+        ap.error("--config4 is not the headline run: give --full with it")
+    if args.config4 and args.dump_outputs:
+        ap.error("--dump-outputs writes the headline run's outputs, not --config4's")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
@@ -384,14 +511,14 @@ def main():
             dist.destroy_process_group()
         return
 
-    buf, own_len, off, file_len, n_own = make_shard(int(args.size), args.seed, rank, world,
-                                                    threads, dist, cdev)
-    dcomp = torch.empty(len(buf) + 64, dtype=torch.uint8, device=dev)
-    dcomp[len(buf):].zero_()
-    dcomp[:len(buf)].copy_(torch.from_numpy(buf), non_blocking=False)
-    torch.cuda.synchronize()
+    pieces, own_len, off, file_len, n_own = make_shard(int(args.size), args.seed, rank, world,
+                                                       threads, dist, cdev)
+    dcomp, n_buf = upload_pieces(pieces, dev)
+    # the range as host bytes: only what --full runs on the host reads it
+    buf = np.concatenate(pieces) if args.full else None
+    del pieces
     # FileVirtualSplit of this rank's FileSplit [off, off + own_len) (BAMInputFormat.java:181-190)
-    rc, g, err = ctx.guess_batch(dcomp[:len(buf)], np.array([0], np.int64),
+    rc, g, err = ctx.guess_batch(dcomp[:n_buf], np.array([0], np.int64),
                                  np.array([own_len], np.int64), N_REF)
     if rc or err[0] or int(g[0]) == own_len:
         raise RuntimeError("no record start in rank %d's split (rc %d err %d)" % (rank, rc, err[0]))
@@ -399,7 +526,7 @@ def main():
     v_end = ((off + own_len) << 16) | 0xffff
 
     def step():
-        rc, cols = ctx.decode_split_device(dcomp[:len(buf)], v_start, v_end, N_REF, comp_base=off,
+        rc, cols = ctx.decode_split_device(dcomp[:n_buf], v_start, v_end, N_REF, comp_base=off,
                                            file_len=file_len)
         if rc != 0 or cols.status != 0:
             raise RuntimeError("decode failed rc=%d status=%d: %s" % (rc, cols.status, ctx.last_error()))
@@ -424,9 +551,11 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.time() - t0
 
-    # ---- outside the timed region: record-count check, roofline inputs, parity
+    # ---- outside the timed region: the outputs, the record-count check; with --full parity, baseline
     n_rec = int(cols.n_records)
     ubytes = int(stages[-1]["ubuf_bytes"])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, cols, int(stages[-1]["pool_bytes"]), args.dump_outputs)
     overlap = 0
     if rank > 0 and n_rec:
         # records of the block that starts exactly at this split's beginning: the previous split
@@ -455,7 +584,9 @@ def main():
                            % (rec_all, ovl_all, gen_all))
     parity = None
     whole_res = None
-    if not args.no_whole_check:
+    if not args.full:
+        pass  # a plain run: the headline alone
+    elif not args.no_whole_check:
         # every record of the timed launch against the oracle, on every rank (its own shard); at
         # most WHOLE_CHECK_GROUP ranks hold their host copy (~2.3 x U) at once
         for turn in range(0, world, WHOLE_CHECK_GROUP):
@@ -463,7 +594,7 @@ def main():
                 whole_res, hc = whole_shard_check(ctx, cols, buf, own_len, off, threads)
                 if rank == 0 and args.parity_splits > 0 and hc is not None:
                     try:
-                        parity = parity_at_size(ctx, buf, dcomp[:len(buf)], args.parity_splits,
+                        parity = parity_at_size(ctx, buf, dcomp[:n_buf], args.parity_splits,
                                                 args.seed + 17, threads, whole=host_views(hc))
                     except Exception as e:  # reported, never hidden
                         parity = {"error": str(e)}
@@ -484,7 +615,7 @@ def main():
             hc = _lib.Columns()
             if ctx.L.hbam_columns_to_host(ctx.h, C.byref(cols), C.byref(hc)):
                 raise RuntimeError("hbam_columns_to_host: %s" % ctx.last_error())
-            parity = parity_at_size(ctx, buf, dcomp[:len(buf)], args.parity_splits, args.seed + 17,
+            parity = parity_at_size(ctx, buf, dcomp[:n_buf], args.parity_splits, args.seed + 17,
                                     threads, whole=host_views(hc))
             ctx.L.hbam_free_host_columns(C.byref(hc))
         except Exception as e:  # reported, never hidden
@@ -495,7 +626,7 @@ def main():
     result = headline(args, world, elapsed, stages, huff_ms, ubytes, n_rec, own_len, file_len,
                       ub_all, rec_all, parity) if rank == 0 else None
     del cols
-    if dist and not args.no_sort:
+    if dist and args.full and not args.no_sort:
         # config #5's leg across the ranks (cli/plugins/Sort.java:131-170), after the headline's timed
         # region: decode + device sort + split points + exchange by key range (hbam_sort_exchange
         # over RCCL on nccl), with its own parity (tools/sort_leg.py)
@@ -503,7 +634,7 @@ def main():
         if rank == 0:
             result["sort"] = res
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:  # the CPU baseline: rank 0 at N = 1 only
+        if args.full and world == 1 and not args.no_cpu_baseline:  # the CPU baseline: rank 0 at N = 1 only
             try:
                 result["cpu_baseline"] = cpu_baseline(buf, args.cpu_budget, threads)
             except Exception as e:  # baseline is reported, never the target
@@ -609,7 +740,8 @@ def headline(args, world, elapsed, stages, huff_ms, ubytes, n_rec, own_len, file
         "metric": METRIC, "value": round(value, 3), "unit": "GB/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(per_step * 1e3, 3),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
-        "data": "synthetic (tools/gen_bam.cpp: seeded 150bp PE, zlib level 5, BGZF)",
+        "data": "synthetic (tools/gen_bam.cpp: seeded 150bp PE, zlib level 5, BGZF; %d copies per GPU of one "
+                "generated body)" % BODY_COPIES,
         "config": {"workload": "config#2 per GPU (config#4 shape for N>1): ~10 GB compressed "
                                "coordinate-sorted 150bp PE BAM per GPU, one file of N x 10 GB "
                                "sharded by byte range into guess-aligned FileVirtualSplits, BGZF "

@@ -1,4 +1,4 @@
-"""`bench.py --config4`: BASELINE config #4 — ONE 200 GB synthetic BAM decoded by N GPUs, each rank
+"""`bench.py --full --config4`: BASELINE config #4 — ONE 200 GB synthetic BAM decoded by N GPUs, each rank
 its byte range of the file (200/N GB compressed) resident in HBM (strong scaling: the total is fixed).
 
 The file is built so that 200 GB can exist without 200 GB of generator time: the BAM header's BGZF

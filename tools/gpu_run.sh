@@ -6,7 +6,7 @@
 #   tests[,EXPR]         pytest -m gpu (optionally -k EXPR)
 #   testslib,LIB[,EXPR] the same against hadoop-bam_amd/LIB (HBAM_LIB)
 #   smoke                __graft_entry__.smoke()
-#   bench[,STEPS]        python bench.py (default --steps 20 --warmup 3)
+#   bench[,STEPS]        python bench.py --full (default --steps 20 --warmup 3)
 #   prof                 rocprofv3 --kernel-trace --stats of a short bench.py run
 #   pmc,COUNTERS[,SIZE[,LIB]]  one rocprofv3 --pmc pass (COUNTERS separated by '+') over a decode
 #   pmcbytes[,SIZE]      FETCH_SIZE + WRITE_SIZE passes over a decode, folded by tools/pmc_summarize.py
@@ -39,9 +39,9 @@ for spec in "$@"; do
     smoke)
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; r=$? ;;
     bench)
-      timeout -k 10 600 python -u bench.py --steps ${a1:-20} --warmup 3 > $O/bench.json 2> $O/bench.err; r=$? ;;
+      timeout -k 10 600 python -u bench.py --full --steps ${a1:-20} --warmup 3 > $O/bench.json 2> $O/bench.err; r=$? ;;
     prof)
-      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --parity-splits 0 --no-whole-check > $O/bench_prof.json 2> $O/prof.err; r=$? ;;
+      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python3 bench.py --steps 5 --warmup 1 > $O/bench_prof.json 2> $O/prof.err; r=$? ;;
     pmc)  # pmc,COUNTERS[,SIZE[,LIB]]: one counter pass over a decode (csv per dispatch)
       P=$O/pmc_${a1//+/_}${a3:+_$a3}
       timeout -s KILL 300 rocprofv3 --pmc ${a1//+/ } -d $P -o run --output-format csv -- python3 tools/ab_decode.py --size ${a2:-2e9} --reps 1 --digest 0 --libs ${a3:-libhbam.so} > $P.txt 2>&1; r=$? ;;

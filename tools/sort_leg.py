@@ -1,4 +1,4 @@
-"""Config #5's leg of `bench.py --gpus N` (N > 1): the coordinate Sort plugin across the ranks.
+"""Config #5's leg of `bench.py --full --gpus N` (N > 1): the coordinate Sort plugin across the ranks.
 
 Run after the headline's timed decode, by every rank (cli/plugins/Sort.java:84-188: SortRecordReader
 keys, TotalOrderPartitioner over sampled split points :131-157, the shuffle, identity SortReducer
