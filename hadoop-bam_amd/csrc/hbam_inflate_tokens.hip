@@ -33,10 +33,12 @@ __global__ __launch_bounds__(INFLATE_WG, 2) void k_inflate_tokens(const uint8_t*
                                                                   uint8_t* __restrict__ edges,
                                                                   int32_t* __restrict__ status,
                                                                   const uint32_t* __restrict__ list,
-                                                                  const uint32_t* __restrict__ nlist) {
+                                                                  const uint32_t* __restrict__ nlist,
+                                                                  uint32_t tok_generic) {
   // 320 B of LDS per lane (u8 lit/len + distance symbols): 20 KiB per workgroup -> 8 per CU
   __shared__ uint8_t s_ll[INFLATE_WG * 288];
   __shared__ uint8_t s_d[INFLATE_WG * 32];
+  // tok_generic != 0 (env HBAM_TOK_GENERIC=1): the generic symbol loop only (inflate_tok.h tok_symbols)
   // list mode: the blocks k_inflate_wave left (list[0 .. *nlist)), else blocks 0 .. nblk
   uint32_t b = blockIdx.x * INFLATE_WG + threadIdx.x;
   if (list) {
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(INFLATE_WG, 2) void k_inflate_tokens(const uint8_t*
     uint8_t* const my_d = s_d + threadIdx.x * 32;
     st = inflate_tokens_block(comp + r.coff + 18, r.clen - 26u, r.isize, my_ll, my_d,
                               lens_scratch + (uint64_t)b * LENS_SLOT, sink,
-                              &produced
+                              &produced, tok_generic
 #ifdef HBAM_PROF
                               , pt, pc
 #endif

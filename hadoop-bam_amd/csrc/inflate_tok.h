@@ -43,6 +43,10 @@ namespace hbam {
   } while (0)
 #define TOK_PC(i) (void)0
 #endif
+// CPU model only (tools/cpu_model/tok_model.cpp): counts the symbol-loop entries per body
+#ifndef TOK_BODY_ENTERED
+#define TOK_BODY_ENTERED(v) (void)0
+#endif
 
 constexpr uint32_t TOK_K = 4;  // symbol-loop iterations per input epoch (power of two)
 
@@ -258,14 +262,41 @@ __device__ __forceinline__ void huffp_make(const Huff& h, HuffP& p) {
   "v_dot2_u32_u16 %[so], %[g], " DA ", %[so]\n\t"     \
   "v_dot2_u32_u16 %[sl], %[h], %[one], %[sl]\n\t"     \
   "v_dot2_u32_u16 %[so], %[h], " DB ", %[so]\n\t"
-template <bool HI>
+// Specialised pair ranges [P0, P1) (tok_symbols picks them per wave from tok_build's TOK_FIT_* bits):
+//   P0 = 1: the code has no length 1 or 2, so lim[0] == lim[1] == 0 and pair 0 always gives g = (1,1);
+//           its sums are per-lane constants, folded into o0 / t0 by huffp_fold and into the length base here;
+//   P1 < 7: the code is complete with no length above 2 * P1 - 1, so every limit from pair P1 on is 32768
+//           and its compares never hold.
+// A specialised range is only ever given a complete code, where v < lim14 (== 32768) always holds.
+template <bool HI, int P0 = 0, int P1 = 7>
 __device__ __forceinline__ bool huffp_lookup(const HuffP& h, uint32_t v, uint32_t& L, uint32_t& idx,
                                              uint32_t& hi) {
+  constexpr bool ALL = P0 == 0 && P1 == 7;
+  static_assert(ALL || (HI && P0 == 1 && P1 == 7) || (!HI && P0 == 1 && P1 == 5),
+                "huffp_lookup: pair range without an instruction sequence");
   const uint32_t vv = (v + 1u) * 0x10001u;  // v + 1 <= 32768 in both halves
   const uint32_t one = 0x10001u;
   uint32_t sl = 0, so = 0, st = 0, g;
   uint32_t g2;
-  if (HI) {
+  if (HI && !ALL) {  // lit/len, pairs 1..6
+    asm(HBAM_PK2_PAIR("%[l1]", "%[d1]", "%[t1]", "%[l2]", "%[d2]", "%[t2]")
+        HBAM_PK2_PAIR("%[l3]", "%[d3]", "%[t3]", "%[l4]", "%[d4]", "%[t4]")
+        : [sl] "+v"(sl), [so] "+v"(so), [st] "+v"(st), [g] "=&v"(g), [h] "=&v"(g2)
+        : [vv] "v"(vv), [one] "v"(one), [l1] "v"(h.lim[1]), [l2] "v"(h.lim[2]), [l3] "v"(h.lim[3]),
+          [l4] "v"(h.lim[4]), [d1] "v"(h.dof[1]), [d2] "v"(h.dof[2]), [d3] "v"(h.dof[3]),
+          [d4] "v"(h.dof[4]), [t1] "v"(h.dhl[1]), [t2] "v"(h.dhl[2]), [t3] "v"(h.dhl[3]),
+          [t4] "v"(h.dhl[4]));
+    asm(HBAM_PK2_PAIR("%[l5]", "%[d5]", "%[t5]", "%[l6]", "%[d6]", "%[t6]")
+        : [sl] "+v"(sl), [so] "+v"(so), [st] "+v"(st), [g] "=&v"(g), [h] "=&v"(g2)
+        : [vv] "v"(vv), [one] "v"(one), [l5] "v"(h.lim[5]), [l6] "v"(h.lim[6]), [d5] "v"(h.dof[5]),
+          [d6] "v"(h.dof[6]), [t5] "v"(h.dhl[5]), [t6] "v"(h.dhl[6]));
+  } else if (!ALL) {  // distance, pairs 1..4
+    asm(HBAM_PK2_PAIR_NT("%[l1]", "%[d1]", "%[l2]", "%[d2]") HBAM_PK2_PAIR_NT("%[l3]", "%[d3]", "%[l4]", "%[d4]")
+        : [sl] "+v"(sl), [so] "+v"(so), [g] "=&v"(g), [h] "=&v"(g2)
+        : [vv] "v"(vv), [one] "v"(one), [l1] "v"(h.lim[1]), [l2] "v"(h.lim[2]), [l3] "v"(h.lim[3]),
+          [l4] "v"(h.lim[4]), [d1] "v"(h.dof[1]), [d2] "v"(h.dof[2]), [d3] "v"(h.dof[3]),
+          [d4] "v"(h.dof[4]));
+  } else if (HI) {
     asm(HBAM_PK2_PAIR("%[l0]", "%[d0]", "%[t0]", "%[l1]", "%[d1]", "%[t1]")
         HBAM_PK2_PAIR("%[l2]", "%[d2]", "%[t2]", "%[l3]", "%[d3]", "%[t3]")
         : [sl] "+v"(sl), [so] "+v"(so), [st] "+v"(st), [g] "=&v"(g), [h] "=&v"(g2)
@@ -288,11 +319,18 @@ __device__ __forceinline__ bool huffp_lookup(const HuffP& h, uint32_t v, uint32_
           [d0] "v"(h.dof[0]), [d1] "v"(h.dof[1]), [d2] "v"(h.dof[2]), [d3] "v"(h.dof[3]),
           [d4] "v"(h.dof[4]), [d5] "v"(h.dof[5]), [d6] "v"(h.dof[6]));
   }
-  const uint32_t l = 1u + sl;
+  const uint32_t l = 1u + 2u * (uint32_t)P0 + sl;
   L = l;
   idx = (h.o0 + so + (v >> (15u - l))) & 0xffffu;
   if (HI) hi = v >= ((h.t0 + st) & 0xffffu) ? 256u : 0u;
-  return v < h.lim14;
+  return ALL ? v < h.lim14 : true;
+}
+// the table a lookup with P0 = 1 takes: pair 0's constant sums (g = (1,1)) moved into o0 and t0
+__device__ __forceinline__ HuffP huffp_fold(const HuffP& p) {
+  HuffP f = p;
+  f.o0 = p.o0 + (p.dof[0] & 0xffffu) + (p.dof[0] >> 16);
+  f.t0 = p.t0 + (p.dhl[0] & 0xffffu) + (p.dhl[0] >> 16);
+  return f;
 }
 
 // ---- output ------------------------------------------------------------------------------
@@ -448,10 +486,16 @@ __device__ __forceinline__ uint32_t quad_byte(const uint4& q, uint32_t j) {  // 
   const uint32_t w = j < 4 ? q.x : j < 8 ? q.y : j < 12 ? q.z : q.w;
   return (w >> (8u * (j & 3u))) & 0xffu;
 }
+// Returns 0 for a set zlib rejects, else TOK_BUILT plus what a specialised symbol loop may rely on:
+//   TOK_FIT_FULL  the code is complete (so lim[14] == 32768: every 15-bit value starts a code);
+//   TOK_FIT_LOW   ... and has no code of length 1 or 2 (lim[0] == lim[1] == 0);
+//   TOK_FIT_M11   ... and none longer than 11 (lim[10 ..] == 32768).
+// The incomplete-but-legal sets (a single distance code, no distance code) get none of them.
+constexpr uint32_t TOK_BUILT = 1u, TOK_FIT_FULL = 2u, TOK_FIT_LOW = 4u, TOK_FIT_M11 = 8u;
 // Out of line: called once per DEFLATE block, and inlining its unrolled counters into the
 // kernel pushes the symbol loop's state into scratch.
-__device__ __attribute__((noinline)) bool tok_build(const uint8_t* __restrict__ lens, int n,
-                                                    uint8_t* __restrict__ syms, Huff& h, int kind) {
+__device__ __attribute__((noinline)) uint32_t tok_build(const uint8_t* __restrict__ lens, int n,
+                                                        uint8_t* __restrict__ syms, Huff& h, int kind) {
   typedef uint8_t SymT;
   const uint4* lq = (const uint4*)lens;
   const int nq = (n + 15) >> 4;
@@ -478,6 +522,7 @@ __device__ __attribute__((noinline)) bool tok_build(const uint8_t* __restrict__ 
 #pragma unroll
   for (int L = 1; L < 16; ++L) maxl = cnt[L] ? (uint32_t)L : maxl;
   h.empty = (maxl == 0);
+  uint32_t fit = TOK_BUILT;
   if (maxl != 0) {
     int32_t left = 1;
     bool over = false;
@@ -486,8 +531,13 @@ __device__ __attribute__((noinline)) bool tok_build(const uint8_t* __restrict__ 
       left = 2 * left - (int32_t)cnt[L];
       over |= left < 0;
     }
-    if (over) return false;
-    if (left > 0 && (kind == 0 || maxl != 1)) return false;  // incomplete set
+    if (over) return 0u;
+    if (left > 0 && (kind == 0 || maxl != 1)) return 0u;  // incomplete set
+    if (left == 0) {
+      fit |= TOK_FIT_FULL;
+      fit |= (cnt[1] | cnt[2]) == 0u ? TOK_FIT_LOW : 0u;
+      fit |= maxl <= 11u ? TOK_FIT_M11 : 0u;
+    }
   }
   uint32_t code = 0, base = 0;
   uint32_t next[16];
@@ -527,7 +577,7 @@ __device__ __attribute__((noinline)) bool tok_build(const uint8_t* __restrict__ 
       }
     }
   }
-  return true;
+  return fit;
 }
 
 // One iteration of the symbol loop with >= 64 stream bits left: two lit/len codes + length
@@ -565,16 +615,20 @@ struct TPend {
     em = false;
   }
 };
+// SPEC: the specialised lookups (lit/len pairs 1..6, distance pairs 1..4) on tables folded by
+// huffp_fold; they return a constant true (a complete code), so the ok1 / ok2 / okd tests and the
+// selects that hang off them fold away.
+template <bool SPEC>
 __device__ __forceinline__ uint32_t tok_fast_spec(EIn& in, const HuffP& hl, const HuffP& hd,
                                                   const uint8_t* __restrict__ syms_ll,
                                                   const uint8_t* __restrict__ syms_d, TSink& sink,
                                                   uint32_t& op, uint32_t isize, TPend& pd) {
   ein_refill_sel(in);
   uint32_t L1, idx1, hi1 = 0, L2, idx2, hi2 = 0;
-  const bool ok1 = huffp_lookup<true>(hl, ein_rev15(in), L1, idx1, hi1);
+  const bool ok1 = huffp_lookup<true, SPEC ? 1 : 0, 7>(hl, ein_rev15(in), L1, idx1, hi1);
   const uint32_t l1 = ok1 ? L1 : 0u;
   const uint32_t v2 = __builtin_bitreverse32((uint32_t)(in.bb >> l1)) >> 17;
-  const bool ok2 = huffp_lookup<true>(hl, v2, L2, idx2, hi2);
+  const bool ok2 = huffp_lookup<true, SPEC ? 1 : 0, 7>(hl, v2, L2, idx2, hi2);
   const uint32_t sym1 = (uint32_t)syms_ll[ok1 ? idx1 : 0u] | hi1;
   const uint32_t sym2 = (uint32_t)syms_ll[ok2 ? idx2 : 0u] | hi2;
   sink.put(pd.op1, pd.P, pd.nb);  // the previous iteration's packet
@@ -603,7 +657,7 @@ __device__ __forceinline__ uint32_t tok_fast_spec(EIn& in, const HuffP& hl, cons
   const uint32_t mlen = lbase + ein_peek(in, lext);
   ein_drop(in, lext);
   uint32_t L, idx, dh;
-  const bool okd = huffp_lookup<false>(hd, ein_rev15(in), L, idx, dh);
+  const bool okd = huffp_lookup<false, SPEC ? 1 : 0, SPEC ? 5 : 7>(hd, ein_rev15(in), L, idx, dh);
   const uint32_t dsym = syms_d[okd ? idx : 0u];
   sink.mark_if(pd.em, pd.opm);  // the previous iteration's match mark
   ex = (dom && !okd) ? 3u : ex;
@@ -681,13 +735,67 @@ __device__ __forceinline__ uint32_t tok_careful(EIn& in, const HuffP& hl, const 
   return n < mlen ? 2u : 0u;
 }
 
+// The symbol loop of one Huffman-coded DEFLATE block; returns the lane's exit code (1 end of block,
+// 2 leave (zlib stops), 3 data error).  SPEC: every lane that enters has complete lit/len and
+// distance codes without lengths 1 and 2 and no distance code longer than 11 bits (tok_build's
+// TOK_FIT_* bits), which is what BAM bodies at zlib's default levels give (profiles/
+// huffman_length_ranges/ranges.txt): the fast path then runs the shorter lookups (tok_fast_spec).
+// The careful symbol keeps the generic lookup on the unfolded tables.
+// One structured loop (no continue / goto inside): every path of an iteration joins at
+// the loop's end with an exit code, so the decoder state needs no per-path copies.
+template <bool SPEC>
+__device__ __forceinline__ uint32_t tok_symbols(EIn& in, const HuffP& hl, const HuffP& hd,
+                                                const uint8_t* __restrict__ syms_ll,
+                                                const uint8_t* __restrict__ syms_d, TSink& sink,
+                                                uint32_t& op, uint32_t isize, uint32_t& it
+#ifdef HBAM_PROF
+                                                , uint64_t* pt, uint64_t* pc, uint64_t& tq
+#endif
+                                                ) {
+  const HuffP fl = SPEC ? huffp_fold(hl) : hl, fd = SPEC ? huffp_fold(hd) : hd;
+  uint32_t ex = 0;  // 0 next symbol, 1 end of block, 2 leave (zlib stops), 3 data error
+  TPend pd;
+  pd.clear();
+  // A wave-uniform loop (the exit is a ballot): a lane whose block has ended idles in it, as
+  // it idled at the exit of a divergent loop, without the per-iteration exec-mask bookkeeping
+  // of one.  The careful symbol (a lane's last 64 stream bits) runs behind a wave-uniform test.
+  // With the predicated match mark and the branch-free bases: Huffman 31.1 -> 30.65 ms at
+  // 5 GB, same output (profiles/r05/ab/huffman_uniform_loop_5g.txt).
+  for (;;) {
+    TOK_PC(0);
+#ifdef HBAM_PROF
+    TOK_PT(2);
+#endif
+    if ((__builtin_amdgcn_readfirstlane(++it) & (TOK_K - 1u)) == 0u) ein_epoch(in);
+#ifdef HBAM_PROF
+    TOK_PT(0);  // the epoch: merge (waits for the quad in flight) + the next request
+#endif
+    const bool run = ex == 0u && !ein_short(in, TOK_FAST_BITS);
+    const bool fast = in.total - in.consumed >= TOK_FAST_BITS;
+    if (run && fast) ex = tok_fast_spec<SPEC>(in, fl, fd, syms_ll, syms_d, sink, op, isize, pd);
+    if (__builtin_amdgcn_ballot_w64(run && !fast) != 0u) {
+      if (run && !fast) {
+        pd.flush(sink);
+        ex = tok_careful(in, hl, hd, syms_ll, syms_d, sink, op, isize);
+      }
+    }
+#ifdef HBAM_PROF
+    TOK_PT(1);
+#endif
+    if (__builtin_amdgcn_ballot_w64(ex == 0u) == 0u) break;
+  }
+  pd.flush(sink);  // the last fast iteration's packet and mark
+  return ex;
+}
+
 // Inflate one raw DEFLATE stream (cdata, nbytes) to exactly isize bytes into the token sink.
 // syms_ll: 288 u8 LDS slots (symbol & 255; bit 8 from Huff.hlim); syms_d: 32 u8 LDS slots;
-// lens: LENS_SLOT bytes of 16-aligned global scratch.  Returns INF_OK / INF_SHORT / INF_DATA.
+// lens: LENS_SLOT bytes of 16-aligned global scratch.  tok_generic (wave-uniform): never take the
+// specialised symbol loop.  Returns INF_OK / INF_SHORT / INF_DATA.
 __device__ __forceinline__ int32_t inflate_tokens_block(const uint8_t* __restrict__ cdata, uint32_t nbytes,
                                         uint32_t isize, uint8_t* __restrict__ syms_ll,
                                         uint8_t* __restrict__ syms_d, uint8_t* __restrict__ lens,
-                                        TSink& sink, uint32_t* produced
+                                        TSink& sink, uint32_t* produced, uint32_t tok_generic
 #ifdef HBAM_PROF
                                         , uint64_t* pt, uint64_t* pc
 #endif
@@ -699,6 +807,7 @@ __device__ __forceinline__ int32_t inflate_tokens_block(const uint8_t* __restric
   ein_init(in, cdata, nbytes);
   uint32_t op = 0;
   HuffP hl, hd;
+  uint32_t fit_ll = 0, fit_d = 0;  // tok_build's TOK_FIT_* bits of hl / hd
   bool last = false;
   int32_t rc = INF_OK;
   uint32_t it = 0;  // iteration counter shared by the lanes of a phase (epoch clock)
@@ -740,9 +849,9 @@ __device__ __forceinline__ int32_t inflate_tokens_block(const uint8_t* __restric
         uint32_t* d32 = (uint32_t*)(lens + TOK_LENS_D);
         for (int s = 0; s < 32; s += 4) d32[s / 4] = 0x05050505u;
         Huff t;
-        tok_build(lens + TOK_LENS_LL, 288, syms_ll, t, 1);
+        fit_ll = tok_build(lens + TOK_LENS_LL, 288, syms_ll, t, 1);
         huffp_make(t, hl);
-        tok_build(lens + TOK_LENS_D, 32, syms_d, t, 2);
+        fit_d = tok_build(lens + TOK_LENS_D, 32, syms_d, t, 2);
         huffp_make(t, hd);
       } else if (type == 2u) {
         ein_ensure(in, 64);
@@ -847,9 +956,9 @@ __device__ __forceinline__ int32_t inflate_tokens_block(const uint8_t* __restric
         if (lens[TOK_LENS_LL + 256] == 0) { rc = INF_DATA; goto done; }
         {
           Huff t;
-          if (!tok_build(lens + TOK_LENS_LL, (int)nlen, syms_ll, t, 1)) { rc = INF_DATA; goto done; }
+          if (!(fit_ll = tok_build(lens + TOK_LENS_LL, (int)nlen, syms_ll, t, 1))) { rc = INF_DATA; goto done; }
           huffp_make(t, hl);
-          if (!tok_build(lens + TOK_LENS_D, (int)ndist, syms_d, t, 2)) { rc = INF_DATA; goto done; }
+          if (!(fit_d = tok_build(lens + TOK_LENS_D, (int)ndist, syms_d, t, 2))) { rc = INF_DATA; goto done; }
           huffp_make(t, hd);
         }
 #ifdef HBAM_PROF
@@ -864,43 +973,27 @@ __device__ __forceinline__ int32_t inflate_tokens_block(const uint8_t* __restric
     // `s_waitcnt vmcnt(n)` on the distance tables into every iteration, which also waits for
     // the iteration's own output stores.
     __builtin_amdgcn_s_waitcnt(0);
-    // ---- symbols of a Huffman-coded block
-    // One structured loop (no continue / goto inside): every path of an iteration joins at
-    // the loop's end with an exit code, so the decoder state needs no per-path copies.
+    // ---- symbols of a Huffman-coded block: tok_symbols, in the body the wave's tables allow.
+    // One ballot over the lanes that enter the loop (a lane with a stored block, a finished or a
+    // failed one is not here and so has no say) and a scalar branch; nothing inside the iteration.
     TOK_PT(6);  // header + tables
     {
-      uint32_t ex = 0;  // 0 next symbol, 1 end of block, 2 leave (zlib stops), 3 data error
-      TPend pd;
-      pd.clear();
-      // A wave-uniform loop (the exit is a ballot): a lane whose block has ended idles in it, as
-      // it idled at the exit of a divergent loop, without the per-iteration exec-mask bookkeeping
-      // of one.  The careful symbol (a lane's last 64 stream bits) runs behind a wave-uniform test.
-      // With the predicated match mark and the branch-free bases: Huffman 31.1 -> 30.65 ms at
-      // 5 GB, same output (profiles/r05/ab/huffman_uniform_loop_5g.txt).
-      for (;;) {
-        TOK_PC(0);
+      const uint32_t fit = tok_generic ? 0u : (fit_ll & fit_d);
+      const bool mine = (fit & TOK_FIT_LOW) != 0u && (fit_d & TOK_FIT_M11) != 0u;
+      uint32_t ex;
 #ifdef HBAM_PROF
-        TOK_PT(2);
+#define TOK_SYMBOLS_ARGS in, hl, hd, syms_ll, syms_d, sink, op, isize, it, pt, pc, tq
+#else
+#define TOK_SYMBOLS_ARGS in, hl, hd, syms_ll, syms_d, sink, op, isize, it
 #endif
-        if ((__builtin_amdgcn_readfirstlane(++it) & (TOK_K - 1u)) == 0u) ein_epoch(in);
-#ifdef HBAM_PROF
-        TOK_PT(0);  // the epoch: merge (waits for the quad in flight) + the next request
-#endif
-        const bool run = ex == 0u && !ein_short(in, TOK_FAST_BITS);
-        const bool fast = in.total - in.consumed >= TOK_FAST_BITS;
-        if (run && fast) ex = tok_fast_spec(in, hl, hd, syms_ll, syms_d, sink, op, isize, pd);
-        if (__builtin_amdgcn_ballot_w64(run && !fast) != 0u) {
-          if (run && !fast) {
-            pd.flush(sink);
-            ex = tok_careful(in, hl, hd, syms_ll, syms_d, sink, op, isize);
-          }
-        }
-#ifdef HBAM_PROF
-        TOK_PT(1);
-#endif
-        if (__builtin_amdgcn_ballot_w64(ex == 0u) == 0u) break;
+      if (__builtin_amdgcn_ballot_w64(!mine) == 0u) {
+        TOK_BODY_ENTERED(1);
+        ex = tok_symbols<true>(TOK_SYMBOLS_ARGS);
+      } else {
+        TOK_BODY_ENTERED(0);
+        ex = tok_symbols<false>(TOK_SYMBOLS_ARGS);
       }
-      pd.flush(sink);  // the last fast iteration's packet and mark
+#undef TOK_SYMBOLS_ARGS
       if (ex == 2u) goto leave;
       if (ex == 3u) {
         rc = INF_DATA;

@@ -10,10 +10,21 @@
 // malloc'd fresh per block and never cleared, so a read of a slot the decode has not written that
 // reaches a branch, an address or the compared output is reported by MSan with its origin.
 // Built by tools/cpu_model/build.py; tests/test_cpu_model.py runs it.
+//
+// The current source picks a symbol-loop body per DEFLATE block (tok_symbols: the specialised one
+// when the "ballot", here this one lane, finds tables that fit; HBAM_TOK_GENERIC=1 in the
+// environment forces the generic one, as in the library).  The model counts the loop entries per
+// body, prints the totals, and with -v after the blocks file one line per block
+// (tests/test_tok_spec_model.py).
+#include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#ifdef HBAM_MODEL_BODIES  // the source has tok_symbols (not the r02 one)
+static uint64_t g_body_entries[2];  // [0] generic, [1] specialised
+#define TOK_BODY_ENTERED(v) (++g_body_entries[v])
+#endif
 #include "inflate_tok.h"
 
 using namespace hbam;
@@ -46,6 +57,12 @@ int main(int argc, char** argv) {
     return 2;
   }
   const uint32_t n = hdr[1];
+  const bool verbose = argc > 2 && strcmp(argv[2], "-v") == 0;
+#ifdef HBAM_MODEL_BODIES
+  const char* tg = getenv("HBAM_TOK_GENERIC");
+  const uint32_t tok_generic = tg && strtol(tg, nullptr, 10) != 0 ? 1u : 0u;
+  uint64_t entries[2] = {0, 0};
+#endif
   uint32_t bad = 0, short_ = 0, data = 0;
   uint64_t ubytes = 0;
   for (uint32_t b = 0; b < n; ++b) {
@@ -79,6 +96,9 @@ int main(int argc, char** argv) {
     uint64_t pt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pc[4] = {0, 0, 0, 0};
 #endif
     const int32_t rc = inflate_tokens_block(cbuf + a, clen, isize, syms_ll, syms_d, lens, sink, &produced
+#ifdef HBAM_MODEL_BODIES
+                                            , tok_generic
+#endif
 #ifdef HBAM_PROF
                                             , pt, pc
 #endif
@@ -125,6 +145,16 @@ int main(int argc, char** argv) {
       if (bad <= 10) fprintf(stderr, "block %u: rc %d produced %u isize %u: mismatch\n", b, rc, produced, isize);
     }
     ubytes += isize;
+    if (verbose) {
+      printf("block %u rc %d produced %u ok %d", b, rc, produced, ok ? 1 : 0);
+#ifdef HBAM_MODEL_BODIES
+      printf(" generic %llu specialised %llu", (unsigned long long)(g_body_entries[0] - entries[0]),
+             (unsigned long long)(g_body_entries[1] - entries[1]));
+      entries[0] = g_body_entries[0];
+      entries[1] = g_body_entries[1];
+#endif
+      printf("\n");
+    }
     free(cbuf);
     free(expect);
     free(syms_ll);
@@ -136,5 +166,9 @@ int main(int argc, char** argv) {
     free(ubuf);
   }
   printf("blocks %u bytes %llu bad %u (short %u, data error %u)\n", n, (unsigned long long)ubytes, bad, short_, data);
+#ifdef HBAM_MODEL_BODIES
+  printf("symbol loop entries: generic %llu specialised %llu\n", (unsigned long long)g_body_entries[0],
+         (unsigned long long)g_body_entries[1]);
+#endif
   return bad ? 1 : 0;
 }
