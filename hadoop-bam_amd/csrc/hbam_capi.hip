@@ -176,6 +176,28 @@ enum BufId {
   B_G_BS,
   B_G_PAY,
   B_RH_RECOFF,  // hbam_records_to_host: rec_off rebased to the copied record bytes
+  // BAI index build and region filter (hbam_bai.hip)
+  B_BAI_HAS,
+  B_BAI_W0,
+  B_BAI_W1,
+  B_BAI_COFF,
+  B_BAI_REF,
+  B_BAI_SMALL,
+  B_BAI_KEY,
+  B_BAI_CBEG,
+  B_BAI_CEND,
+  B_BAI_CREC,
+  B_BAI_PERM,
+  B_BAI_LINOFF,
+  B_BAI_LIN,
+  B_BAI_HEAD,
+  B_BAI_HOFF,
+  B_BAI_CK,
+  B_BAI_CB,
+  B_BAI_CE,
+  B_OV_KEEP,
+  B_OV_CNT,
+  B_OV_OFF,
   B_COUNT_ALL
 };
 
@@ -2637,3 +2659,4 @@ extern "C" int64_t hbam_bgzf_compress(hbam_ctx* c, const uint8_t* src, int src_o
 #include "hbam_groups.hip"
 #include "hbam_bcf_api.hip"
 #include "hbam_comm.hip"
+#include "hbam_bai.hip"

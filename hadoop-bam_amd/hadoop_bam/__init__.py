@@ -15,3 +15,4 @@ from .sort import HipSortOps, RcclComm, SortedRun, sort_sharded  # noqa: F401
 from .output import (  # noqa: F401
     BAMRecordWriter, KeyIgnoringBAMOutputFormat, KeyIgnoringBAMRecordWriter, SAMFileHeader,
     SAMOutputPreparer, merge_sam_into, read_sam_header)
+from .index import BAMIndex, BAMIndexer, IndexedBAMReader, parse_region  # noqa: F401

@@ -61,6 +61,7 @@ EXPORTS = [
     "hbam_guess_bcf_windows", "hbam_bcf_decode_split", "hbam_comm_unique_id", "hbam_comm_init",
     "hbam_comm_destroy", "hbam_comm_split_points", "hbam_sort_exchange", "hbam_split_open_reader",
     "hbam_split_read_bytes", "hbam_rewrite_groups", "hbam_records_to_host", "hbam_split_records_to_host",
+    "hbam_bai_bound", "hbam_bai_build", "hbam_overlap_filter",
 ]
 
 # hbam_read_fn: int64_t read(void* user, uint64_t offset, uint64_t len, uint8_t* dst)
@@ -252,6 +253,11 @@ def load(path=None):
         "hbam_comm_destroy": (None, [vp]),
         "hbam_comm_split_points": (C.c_int, [vp, vp, C.POINTER(SortedRunC), C.c_uint32, vp]),
         "hbam_sort_exchange": (C.c_int, [vp, vp, C.POINTER(SortedRunC), vp, C.POINTER(SortedRunC)]),
+        "hbam_bai_bound": (C.c_uint64, [C.c_uint64, C.c_int32]),
+        "hbam_bai_build": (C.c_int64, [vp, C.POINTER(Columns), C.c_int32, C.c_uint64, vp, C.c_uint64,
+                                       C.POINTER(C.c_uint64)]),
+        "hbam_overlap_filter": (C.c_int64, [vp, C.POINTER(Columns), C.c_int32, C.c_int64, C.c_int64,
+                                            C.c_int32, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name, None)
@@ -261,6 +267,25 @@ def load(path=None):
         f.argtypes = args
     _LIB = L
     return L
+
+
+def bgzf_blocks(data, start=0):
+    """Host walk of the BGZF chain of `data` (bytes / numpy / memmap) from file offset `start`:
+    yields (coff, clen, isize, crc) per block, one Python iteration and 26 bytes read each, and
+    stops at the end of the data or at a block the readers would not accept (gzip magic, the BC
+    subfield, BSIZE inside the data: [htsjdk] BlockCompressedInputStream.readBlock's checks)."""
+    a = data if isinstance(data, np.ndarray) else np.frombuffer(data, np.uint8)
+    n, p = len(a), int(start)
+    while p + 18 <= n:
+        h = a[p:p + 18].tobytes()
+        if h[:4] != b"\x1f\x8b\x08\x04" or h[10:16] != b"\x06\x00BC\x02\x00":
+            return
+        clen = (h[16] | h[17] << 8) + 1
+        if clen < 26 or p + clen > n:
+            return
+        crc, isize = (int(x) for x in np.frombuffer(a[p + clen - 8:p + clen].tobytes(), "<u4"))
+        yield p, clen, isize, crc
+        p += clen
 
 
 def host_columns_to_numpy(h):
@@ -647,6 +672,114 @@ class Context:
         if r < 0:
             return int(r), None
         return 0, out[:r]
+
+    def bai_build(self, dcols, n_ref, end_voffset):
+        """hbam_bai_build over the device columns of a whole-file decode -> (rc, .bai bytes or None,
+        err_record): rc < 0 is the exception the indexer raises at record err_record."""
+        cap = int(self.L.hbam_bai_bound(int(dcols.n_records), int(n_ref)))
+        out = np.empty(cap, np.uint8)
+        err = C.c_uint64(0)
+        r = self.L.hbam_bai_build(self.h, C.byref(dcols), int(n_ref), int(end_voffset), out.ctypes.data, cap,
+                                  C.byref(err))
+        if r < 0:
+            return int(r), None, int(err.value)
+        return 0, out[:r].tobytes(), None
+
+    def bai_index(self, data):
+        """The Index plugin's work for one BAM held in host memory (bytes / numpy / memmap): header,
+        whole-file device decode, hbam_bai_build -> (rc, .bai bytes or None, err_record)."""
+        p, n, dev, keep = self._ptr(data)
+        k = min(n, 1 << 20)
+        while True:  # the header from a growing prefix (usually one or two BGZF blocks)
+            h = self.parse_header(data[:k])
+            if isinstance(h, dict) or k >= n:
+                break
+            k = min(n, 4 * k)
+        if not isinstance(h, dict):
+            return h, None, None
+        ev = self.end_voffset(data, h["first_voffset"])
+        d = Columns()
+        rc = self.L.hbam_decode_split(self.h, p, dev, 0, n, n, h["first_voffset"], (n << 16) | 0xffff,
+                                      h["n_ref"], C.byref(d))
+        if rc:
+            return rc, None, None
+        return self.bai_build(d, h["n_ref"], ev)
+
+    @staticmethod
+    def end_voffset(data, first_voffset):
+        """getFilePointer() after the last record a reader gets from a BAM whose first record is at
+        first_voffset: the read ends at the first empty BGZF block after the first record's block
+        (the 28-byte terminator, or an empty block in mid-file), else at the end of the file; the
+        stream has then consumed the block before it and points at that block's start.  A host
+        walk of the block headers (bgzf_blocks: host time the device timing of hbam_bai_build does
+        not include; DESIGN.md gives one measurement).  The walk stops at a block the decode would
+        not accept; the decode then raises and no index is built."""
+        first = int(first_voffset) >> 16
+        for coff, _, isize, _ in bgzf_blocks(data, first):
+            if isize == 0 and coff > first:
+                return coff << 16
+        return len(data) << 16
+
+    def overlap_filter(self, dcols, ref_id, beg=0, end=0, contained=False):
+        """hbam_overlap_filter over device columns -> (count, device buffer handle of the kept record
+        indices, ascending u32); the caller frees the handle with device_free."""
+        n = int(dcols.n_records)
+        buf = C.c_void_p()
+        rc = self.L.hbam_device_alloc(self.h, 4 * max(n, 1), C.byref(buf))
+        if rc:
+            raise RuntimeError("hbam_device_alloc failed (%d): %s" % (rc, self.last_error()))
+        k = self.L.hbam_overlap_filter(self.h, C.byref(dcols), int(ref_id), int(beg), int(end),
+                                       int(bool(contained)), buf)
+        if k < 0:
+            self.L.hbam_device_free(self.h, buf)
+            raise RuntimeError("hbam_overlap_filter failed (%d): %s" % (k, self.last_error()))
+        return int(k), buf
+
+    def gather_to_host(self, dcols, idx, k):
+        """Host copy of records idx[0..k) (device u32 indices, e.g. overlap_filter's) of device
+        columns: (voffset u64[k], payload u8 = the records' block_size + bytes packed in that
+        order, offsets u64[k+1]).  Only the k records cross to the host (hbam_gather_records,
+        hbam_permute, hbam_download)."""
+        if k == 0:
+            return np.zeros(0, np.uint64), np.zeros(0, np.uint8), np.zeros(1, np.uint64)
+        vp = C.c_void_p
+        bufs = []
+
+        def alloc(nbytes):
+            b = vp()
+            rc = self.L.hbam_device_alloc(self.h, int(nbytes), C.byref(b))
+            if rc:
+                raise RuntimeError("hbam_device_alloc failed (%d): %s" % (rc, self.last_error()))
+            bufs.append(b)
+            return b
+        try:
+            ubuf, rec_off = C.cast(dcols.ubuf, vp), C.cast(dcols.rec_off, vp)
+            bs, vo = C.cast(dcols.block_size, vp), C.cast(dcols.voffset, vp)
+            off = alloc(8 * (k + 1))
+            tot = C.c_uint64(0)
+            rc = self.L.hbam_gather_records(self.h, ubuf, rec_off, bs, idx, k, None, 0, off, C.byref(tot))
+            if not rc:
+                pay = alloc(max(int(tot.value), 1))
+                rc = self.L.hbam_gather_records(self.h, ubuf, rec_off, bs, idx, k, pay, tot.value, off,
+                                                C.byref(tot))
+            if not rc:
+                dvo = alloc(8 * k)
+                rc = self.L.hbam_permute(self.h, vo, 8, idx, k, dvo)
+            if rc:
+                raise RuntimeError("gathering %d records failed (%d): %s" % (k, rc, self.last_error()))
+            return (self._d2h(dvo.value, k, np.uint64), self._d2h(pay.value, int(tot.value), np.uint8),
+                    self._d2h(off.value, k + 1, np.uint64))
+        finally:
+            for b in bufs:
+                self.L.hbam_device_free(self.h, b)
+
+    def overlap_indices(self, dcols, ref_id, beg=0, end=0, contained=False):
+        """hbam_overlap_filter -> the kept record indices on the host (uint32, ascending)."""
+        k, buf = self.overlap_filter(dcols, ref_id, beg, end, contained)
+        try:
+            return self._d2h(buf.value, k, np.uint32)
+        finally:
+            self.L.hbam_device_free(self.h, buf)
 
     def resolve_tokens(self, tokens, bitmap, tail_token=0, tail_dist=0):
         """Diagnostic: run the LZ77 pass on one token block -> (rc, status, resolved bytes)."""

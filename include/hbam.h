@@ -406,6 +406,31 @@ int64_t hbam_splitting_index(hbam_ctx* ctx, const hbam_columns* dv, int32_t gran
  * Returns the entry count, HBAM_EIO where skipBlock raises IOException, or <0. */
 int64_t hbam_bgzf_block_index(hbam_ctx* ctx, const uint8_t* file, int on_device, uint64_t len,
                               int32_t granularity, uint64_t* out, uint64_t cap);
+/* ---- BAI index and indexed region queries (cli/plugins/Index.java:61-127 -> [htsjdk] BAMIndexer;
+ * cli/plugins/View.java:164-221 -> [htsjdk] SamReader.queryOverlapping).  htsjdk is not in the
+ * reference tree: the rules are restated from memory, parity unpinned (DESIGN.md lists them).
+ * hbam_bai_build: the .bai of a whole-file decode (dv: device columns of hbam_decode_split over
+ * [first record, len<<16|0xffff], as hbam_splitting_index takes them) serialised into `out` (host):
+ * "BAI\1", n_ref, then per reference n_bin, the bins in ascending number (bin, n_chunk, (beg, end)
+ * pairs in file order), the metadata pseudo-bin 37450 ((first, last offset), (records with flag 4
+ * clear, set)), n_intv and the 16 KiB linear index; then u64 n_no_coor.  A record's chunk is
+ * [voffset[i], voffset[i+1]); end_voffset closes the last one (the file pointer after the last
+ * record, by the voffset column's rule).  The stored bin is used as it is.  Returns the byte count
+ * (hbam_bai_bound is always enough; HBAM_EMORE: cap is too small), or the exception the indexer
+ * raises at record *err_record: the decode's own (dv->status), HBAM_EDATA ("Unexpected reference":
+ * a placed record whose refID is smaller than the previous placed record's, or outside [0, n_ref)),
+ * HBAM_EINDEX (a 16 KiB window >= 32768: a position past 2^29).  Timing: total_ms = device time,
+ * n_blocks = chunks written. */
+uint64_t hbam_bai_bound(uint64_t n_records, int32_t n_ref);
+int64_t hbam_bai_build(hbam_ctx* ctx, const hbam_columns* dv, int32_t n_ref, uint64_t end_voffset,
+                       uint8_t* out, uint64_t cap, uint64_t* err_record);
+/* The record filter of an indexed query over one decoded chunk range (dv: device columns): idx_out
+ * (device, u32[dv->n_records]) receives, ascending, the records on ref_id with
+ * start <= end && (alignment end, or start when there is none) >= beg — `contained`: start >= beg &&
+ * that end <= end — in 1-based coordinates; beg <= 0 means 1, end <= 0 the end of the reference.
+ * Returns the count. */
+int64_t hbam_overlap_filter(hbam_ctx* ctx, const hbam_columns* dv, int32_t ref_id, int64_t beg,
+                            int64_t end, int32_t contained, uint32_t* idx_out);
 /* out[i] = src[perm[i]] for elem_size 4 or 8 (device pointers): carries a column (voffset,
  * block_size) through a sort permutation. */
 int hbam_permute(hbam_ctx* ctx, const void* src, uint32_t elem_size, const uint32_t* perm,

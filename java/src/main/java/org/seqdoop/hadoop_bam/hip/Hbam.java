@@ -96,6 +96,11 @@ public final class Hbam implements AutoCloseable {
       FunctionDescriptor.of(I, A, A, I, A, J, A, A, J, A, A, A));
   static final MethodHandle BCF_DECODE_SPLIT = fn("hbam_bcf_decode_split",
       FunctionDescriptor.of(I, A, A, I, J, J, J, A, J, J, A));
+  // BAI index build (cli/plugins/Index) and the record filter of an indexed region query (View)
+  static final MethodHandle BAI_BOUND = fn("hbam_bai_bound", FunctionDescriptor.of(J, J, I));
+  static final MethodHandle BAI_BUILD = fn("hbam_bai_build", FunctionDescriptor.of(J, A, A, I, J, A, J, A));
+  static final MethodHandle OVERLAP_FILTER = fn("hbam_overlap_filter",
+      FunctionDescriptor.of(J, A, A, I, J, J, I, A));
 
   /** hbam_bcf_header: n_contig, n_sample, n_dict, bgzf, header_len, first_voffset (32 bytes). */
   public static final StructLayout BCF_HEADER = MemoryLayout.structLayout(
