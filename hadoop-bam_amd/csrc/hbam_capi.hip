@@ -227,6 +227,7 @@ struct hbam_ctx {
   uint64_t wave_max_blocks = WAVE_MAX_BLOCKS;  // env HBAM_WAVE_MAX_BLOCKS overrides (tests, A/B)
   bool slices_forced = false;                     // ... and then applies to small calls too
   uint32_t tok_generic = 0;  // env HBAM_TOK_GENERIC=1: k_inflate_tokens' generic symbol loop only (tests, A/B)
+  uint32_t tok_interior = 1;  // env HBAM_TOK_INTERIOR=0: its specialised loop without the interior body (tests, A/B)
   hbam_timing timing{};
   uint64_t* pinned_small = nullptr;  // host pinned scalars
   uint64_t guess_batch = GUESS_BATCH;  // env HBAM_GUESS_BATCH overrides (tests: multi-batch)
@@ -552,11 +553,11 @@ int inflate_blocks(hbam_ctx* c, const uint8_t* dcomp, const BlockRec* blk, uint6
                                                          edges + 32 * lo, st + lo, rl, retry + si);
         k_inflate_tokens<<<grid_for(n, INFLATE_WG), INFLATE_WG, 0, c->stream>>>(
             dcomp, blk + lo, uoff + lo, (uint32_t)n, ubuf, lens + lo * LENS_SLOT, bitmap + lo * BITMAP_WORDS,
-            tails + 2 * lo, edges + 32 * lo, st + lo, rl, retry + si, c->tok_generic);
+            tails + 2 * lo, edges + 32 * lo, st + lo, rl, retry + si, c->tok_generic, c->tok_interior);
       } else {
         k_inflate_tokens<<<grid_for(n, INFLATE_WG), INFLATE_WG, 0, c->stream>>>(
             dcomp, blk + lo, uoff + lo, (uint32_t)n, ubuf, lens + lo * LENS_SLOT, bitmap + lo * BITMAP_WORDS,
-            tails + 2 * lo, edges + 32 * lo, st + lo, nullptr, nullptr, c->tok_generic);
+            tails + 2 * lo, edges + 32 * lo, st + lo, nullptr, nullptr, c->tok_generic, c->tok_interior);
       }
       if (ns > 1) {
         HIPCHK(c, hipEventRecord(c->slice_ev[si], c->stream));
@@ -632,6 +633,7 @@ hbam_ctx* hbam_create(int device_ordinal, const hbam_opts* opts) {
   }
   if (const char* wm = getenv("HBAM_WAVE_MAX_BLOCKS")) c->wave_max_blocks = strtoull(wm, nullptr, 10);
   if (const char* tg = getenv("HBAM_TOK_GENERIC")) c->tok_generic = strtol(tg, nullptr, 10) != 0 ? 1u : 0u;
+  if (const char* ti = getenv("HBAM_TOK_INTERIOR")) c->tok_interior = strtol(ti, nullptr, 10) != 0 ? 1u : 0u;
   if (const char* gb = getenv("HBAM_GUESS_BATCH")) {
     const long v = strtol(gb, nullptr, 10);
     if (v > 0) c->guess_batch = (uint64_t)v;

@@ -34,11 +34,13 @@ __global__ __launch_bounds__(INFLATE_WG, 2) void k_inflate_tokens(const uint8_t*
                                                                   int32_t* __restrict__ status,
                                                                   const uint32_t* __restrict__ list,
                                                                   const uint32_t* __restrict__ nlist,
-                                                                  uint32_t tok_generic) {
+                                                                  uint32_t tok_generic,
+                                                                  uint32_t tok_interior) {
   // 320 B of LDS per lane (u8 lit/len + distance symbols): 20 KiB per workgroup -> 8 per CU
   __shared__ uint8_t s_ll[INFLATE_WG * 288];
   __shared__ uint8_t s_d[INFLATE_WG * 32];
   // tok_generic != 0 (env HBAM_TOK_GENERIC=1): the generic symbol loop only (inflate_tok.h tok_symbols)
+  // tok_interior == 0 (env HBAM_TOK_INTERIOR=0): the specialised loop without its interior body
   // list mode: the blocks k_inflate_wave left (list[0 .. *nlist)), else blocks 0 .. nblk
   uint32_t b = blockIdx.x * INFLATE_WG + threadIdx.x;
   if (list) {
@@ -62,7 +64,7 @@ __global__ __launch_bounds__(INFLATE_WG, 2) void k_inflate_tokens(const uint8_t*
     sink.init(ubuf, uoff[b], r.isize, bitmap + (uint64_t)b * BITMAP_WORDS, tails + 2 * (uint64_t)b,
               edges + 32 * (uint64_t)b);
 #ifdef HBAM_PROF
-    uint64_t pt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pc[4] = {0, 0, 0, 0};
+    uint64_t pt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pc[5] = {0, 0, 0, 0, 0};
 #endif
     // per-lane symbol tables, lane-contiguous (dword-interleaving them across the lanes removes
     // the LDS bank conflicts, 75 % of the pass's LDS cycles, but not time: 33.7 vs 34.3 ms at
@@ -72,7 +74,7 @@ __global__ __launch_bounds__(INFLATE_WG, 2) void k_inflate_tokens(const uint8_t*
     uint8_t* const my_d = s_d + threadIdx.x * 32;
     st = inflate_tokens_block(comp + r.coff + 18, r.clen - 26u, r.isize, my_ll, my_d,
                               lens_scratch + (uint64_t)b * LENS_SLOT, sink,
-                              &produced, tok_generic
+                              &produced, tok_generic, tok_interior
 #ifdef HBAM_PROF
                               , pt, pc
 #endif
@@ -80,7 +82,7 @@ __global__ __launch_bounds__(INFLATE_WG, 2) void k_inflate_tokens(const uint8_t*
 #ifdef HBAM_PROF
     if (g_prof) {
       for (int q = 0; q < 8; ++q) g_prof[32 * (uint64_t)b + 16 + q] = pt[q];
-      for (int q = 0; q < 4; ++q) g_prof[32 * (uint64_t)b + 24 + q] = pc[q];
+      for (int q = 0; q < 5; ++q) g_prof[32 * (uint64_t)b + 24 + q] = pc[q];
     }
 #endif
   }

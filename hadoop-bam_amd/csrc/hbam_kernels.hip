@@ -268,7 +268,8 @@ __global__ void k_inflate_tokens(const uint8_t* __restrict__ comp, const BlockRe
                                  uint8_t* __restrict__ lens_scratch, uint32_t* __restrict__ bitmap,
                                  uint32_t* __restrict__ tails, uint8_t* __restrict__ edges,
                                  int32_t* __restrict__ status, const uint32_t* __restrict__ list,
-                                 const uint32_t* __restrict__ nlist, uint32_t tok_generic);
+                                 const uint32_t* __restrict__ nlist, uint32_t tok_generic,
+                                 uint32_t tok_interior);
 #endif
 
 // Huffman pass, one wave (= one workgroup) per BGZF block; see inflate_wave.h.  Blocks it does

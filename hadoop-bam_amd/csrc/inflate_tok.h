@@ -17,8 +17,8 @@
 //   * a lane that would need more bits than its banks hold skips the iteration (stall) until
 //     the next epoch, which only happens on runs of long, far matches.
 // Output (TSink): literals at their final ubuf offsets, a 3-byte descriptor (len-3, dist-1)
-// at the start of every match hole, one bitmap bit per match start (128-position windows
-// written as 16-byte stores), a 16-byte register write-combine chunk for the bytes.
+// at the start of every match hole, one bitmap bit per match start (64-position windows
+// written as 8-byte stores), a 16-byte register write-combine chunk for the bytes.
 // k_resolve (resolve_dev.h) then fills the holes.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -47,6 +47,10 @@ namespace hbam {
 #ifndef TOK_BODY_ENTERED
 #define TOK_BODY_ENTERED(v) (void)0
 #endif
+// ... and the iterations per body (0 generic, 1 specialised, 2 specialised interior)
+#ifndef TOK_ITER
+#define TOK_ITER(v) (void)0
+#endif
 
 constexpr uint32_t TOK_K = 4;  // symbol-loop iterations per input epoch (power of two)
 
@@ -58,6 +62,8 @@ constexpr uint32_t TOK_K = 4;  // symbol-loop iterations per input epoch (power 
 // stream bits one fast-path iteration may consume: 2 lit/len codes + length extra + distance
 // code + distance extra = 15+15+5+15+13 = 63 (<= 64)
 constexpr uint32_t TOK_FAST_BITS = 64u;
+// output bytes one fast-path iteration may produce: two literals and a match of 258
+constexpr uint32_t TOK_ITER_OUT = 260u;
 constexpr uint32_t TOK_LENS_LL = 32;    // lens scratch: lit/len code lengths at +32 ..
 constexpr uint32_t TOK_LENS_D = 320;    //               distance code lengths at +320 (<= 30)
 constexpr uint32_t TOK_LENS_END = 352;  // = LENS_SLOT (hbam_internal.h)
@@ -341,15 +347,16 @@ struct TSink {
   uint32_t curc;    // chunk held in lo/hi (0 at the start: the block's first byte is in chunk 0)
   uint64_t lo, hi;
   uint32_t* bm;     // match-start bitmap of the block (BITMAP_WORDS words)
-  uint32_t bwin;    // 128-position window held in wl (positions 0-63) / wh (64-127)
-  uint32_t nwin;    // windows covering the block
-  uint64_t wl, wh;
+  uint32_t bwin;    // 64-position window held in wl
+  uint32_t nwin;    // windows covering the block (an even count: k_resolve_units reads 128 positions at a time)
+  uint64_t wl;
   uint32_t* tail;   // [0] = op | n<<16 | 1<<31 for a final match shorter than 3 bytes, [1] = dist
   uint32_t t0, t1;  // tail[0..1], stored by finish() (a store behind a branch in the loop cost
                     // every iteration its exec-mask bookkeeping; with the unconditional chunk 0
                     // and the 64-bit bitmap words: Huffman 32.5 -> 31.0 ms at 5 GB, same output,
                     // profiles/r05/ab/huffman_sink_tail_mark_5g.txt)
   uint8_t* edge;    // 32 B: the block's partial first / last 16-byte chunk (k_edge_merge)
+  uint8_t* cdst;    // where the chunk in lo/hi goes when the symbol loop leaves it (flush_cur)
 
   __device__ __forceinline__ void init(uint8_t* ubuf, uint64_t start, uint32_t isize, uint32_t* bmp,
                                        uint32_t* tl, uint8_t* eg) {
@@ -358,11 +365,12 @@ struct TSink {
     soff = (uint32_t)(start & 15u);
     iend = soff + isize;
     curc = 0;  // (a flush before any output writes zeros to the block's own chunk 0 / edge slot)
+    cdst = soff != 0u ? edge : cbase;
     lo = hi = 0;
     bm = bmp;
     bwin = 0;
-    nwin = (isize + 127u) >> 7;
-    wl = wh = 0;
+    nwin = ((isize + 127u) >> 7) * 2u;
+    wl = 0;
     tail = tl;
     t0 = t1 = 0;
   }
@@ -376,35 +384,43 @@ struct TSink {
     uint8_t* dst = full ? cbase + r0 : edge + (r0 < soff ? 0u : 16u);
     st_out((uint4*)dst, make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)));
   }
+  // A chunk the block leaves for a later one is never its last: it is chunk 0 (the edge slot when
+  // the block does not start 16-aligned) or a whole chunk of its own, and cdst says which, set
+  // when the chunk was entered.  Only finish() flushes the last chunk and needs flush()'s test.
+  __device__ __forceinline__ void flush_cur() {
+    st_out((uint4*)cdst, make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)));
+  }
+  __device__ __forceinline__ void enter_if(bool sw, uint32_t c) {
+    uint8_t* const d = cbase + ((uint64_t)c << 4);
+    cdst = sw ? d : cdst;
+  }
   __device__ __forceinline__ void chunk(uint32_t c) {
     if (c != curc) {
       flush();
+      enter_if(true, c);
       curc = c;
       lo = 0;
       hi = 0;
     }
   }
-  __device__ __forceinline__ void win_store() {
-    st_out((uint4*)(bm + 4u * bwin),
-           make_uint4((uint32_t)wl, (uint32_t)(wl >> 32), (uint32_t)wh, (uint32_t)(wh >> 32)));
-  }
+  // One 64-bit word per 64 positions, stored as 8 bytes (the bitmap in memory is what it was when
+  // the window was 128 positions in two words and a 16-byte store; one word halves the selects of
+  // mark_if, and the store rides in a side block the wave enters in nearly every iteration anyway).
+  __device__ __forceinline__ void win_store() { *(uint64_t*)(bm + 2u * bwin) = wl; }
   __device__ __forceinline__ void mark(uint32_t op) { mark_if(true, op); }
   // the match-start bit of op when em: the bit as selects, only the window store behind a branch
   __device__ __forceinline__ void mark_if(bool em, uint32_t op) {
-    const uint32_t w = op >> 7;
+    const uint32_t w = op >> 6;
     if (em && bwin < w) {
       win_store();
-      wl = wh = 0;
+      wl = 0;
       ++bwin;
       while (bwin < w) {  // a match longer than the window: zero windows
         win_store();
         ++bwin;
       }
     }
-    const uint32_t i = op & 127u;
-    const uint64_t m = 1ull << (i & 63u);  // one 64-bit shift and two selects (was four compares)
-    wl |= (em && i < 64u) ? m : 0ull;
-    wh |= (em && i >= 64u) ? m : 0ull;
+    wl |= em ? 1ull << (op & 63u) : 0ull;
   }
   __device__ __forceinline__ void literal(uint32_t op, uint32_t b) {
     const uint32_t r = soff + op;
@@ -432,6 +448,7 @@ struct TSink {
     if (k >= 14u) {  // ... and start the next chunk
       const uint64_t spill = d >> (8u * (16u - k));
       flush();
+      enter_if(true, c + 1u);
       curc = c + 1u;
       lo = spill;
       hi = 0;
@@ -440,7 +457,8 @@ struct TSink {
   }
   // chunk switch as a predicated step: only the flush (a store) sits behind a branch
   __device__ __forceinline__ void switch_if(bool sw, uint32_t c) {
-    if (sw) flush();
+    if (sw) flush_cur();
+    enter_if(sw, c);
     curc = sw ? c : curc;
     lo = sw ? 0ull : lo;
     hi = sw ? 0ull : hi;
@@ -460,7 +478,8 @@ struct TSink {
     hi |= (k > 1u && k < 8u) ? P >> kr : 0ull;
     hi |= k < 8u ? 0ull : P << (8u * kh);
     const bool sp = any && k + nb > 16u;
-    if (sp) flush();
+    if (sp) flush_cur();
+    enter_if(sp, c + 1u);
     const uint64_t spill = P >> (8u * (16u - (k >= 10u ? k : 10u)));
     curc = sp ? c + 1u : curc;
     lo = sp ? spill : lo;
@@ -472,7 +491,7 @@ struct TSink {
     tail[1] = t1;
     while (bwin < nwin) {
       win_store();
-      wl = wh = 0;
+      wl = 0;
       ++bwin;
     }
   }
@@ -618,7 +637,10 @@ struct TPend {
 // SPEC: the specialised lookups (lit/len pairs 1..6, distance pairs 1..4) on tables folded by
 // huffp_fold; they return a constant true (a complete code), so the ok1 / ok2 / okd tests and the
 // selects that hang off them fold away.
-template <bool SPEC>
+// INTERIOR (with SPEC): the caller guarantees op + TOK_ITER_OUT <= isize, so the output cannot fill
+// up in this iteration: no `op == isize` test, the match is never cut short (n == mlen, no tail
+// token, never exit code 2).
+template <bool SPEC, bool INTERIOR = false>
 __device__ __forceinline__ uint32_t tok_fast_spec(EIn& in, const HuffP& hl, const HuffP& hd,
                                                   const uint8_t* __restrict__ syms_ll,
                                                   const uint8_t* __restrict__ syms_d, TSink& sink,
@@ -635,14 +657,14 @@ __device__ __forceinline__ uint32_t tok_fast_spec(EIn& in, const HuffP& hl, cons
   uint32_t ex = ok1 ? 0u : 3u;
   ein_drop(in, l1);
   const bool lit1 = ok1 && hi1 == 0u;
-  ex = (ex == 0u && lit1 && op == isize) ? 2u : ex;
+  if (!INTERIOR) ex = (ex == 0u && lit1 && op == isize) ? 2u : ex;
   const bool emit1 = ex == 0u && lit1;
   const uint32_t op1 = op;
   op += emit1 ? 1u : 0u;
   ex = (emit1 && !ok2) ? 3u : ex;
   ein_drop(in, (emit1 && ok2) ? L2 : 0u);
   const bool lit2 = emit1 && ok2 && hi2 == 0u;
-  ex = (ex == 0u && lit2 && op == isize) ? 2u : ex;
+  if (!INTERIOR) ex = (ex == 0u && lit2 && op == isize) ? 2u : ex;
   const bool emit2 = ex == 0u && lit2;
   op += emit2 ? 1u : 0u;
   const uint32_t m = emit1 ? sym2 : sym1;
@@ -669,15 +691,19 @@ __device__ __forceinline__ uint32_t tok_fast_spec(EIn& in, const HuffP& hl, cons
   dext = dom2 ? dext : 0u;
   const uint32_t dist = dbase + ein_peek(in, dext);
   ein_drop(in, dext);
-  ex = (dom2 && op == isize) ? 2u : ex;
+  if (!INTERIOR) ex = (dom2 && op == isize) ? 2u : ex;
   ex = (dom2 && ex == 0u && dist > op) ? 3u : ex;
   const bool domatch = dom2 && ex == 0u;
-  uint32_t n = isize - op;
-  n = mlen < n ? mlen : n;
-  const bool last = domatch && n < 3u;  // the output filled up inside the match: last token
-  sink.t0 = last ? (op | n << 16 | 0x80000000u) : sink.t0;
-  sink.t1 = last ? dist : sink.t1;
-  const bool em = domatch && n >= 3u;
+  uint32_t n = mlen;
+  bool em = domatch;
+  if (!INTERIOR) {
+    n = isize - op;
+    n = mlen < n ? mlen : n;
+    const bool last = domatch && n < 3u;  // the output filled up inside the match: last token
+    sink.t0 = last ? (op | n << 16 | 0x80000000u) : sink.t0;
+    sink.t1 = last ? dist : sink.t1;
+    em = domatch && n >= 3u;
+  }
   uint64_t P = emit1 ? (uint64_t)(sym1 & 0xffu) : 0ull;
   P |= emit2 ? (uint64_t)(sym2 & 0xffu) << 8 : 0ull;
   const uint32_t nl = (emit1 ? 1u : 0u) + (emit2 ? 1u : 0u);
@@ -688,7 +714,7 @@ __device__ __forceinline__ uint32_t tok_fast_spec(EIn& in, const HuffP& hl, cons
   pd.em = em;
   pd.opm = op;
   op += domatch ? n : 0u;
-  ex = (domatch && n < mlen) ? 2u : ex;
+  if (!INTERIOR) ex = (domatch && n < mlen) ? 2u : ex;
   return ex;
 }
 // One symbol with every zlib outcome checked (the stream's last 64 bits).
@@ -741,13 +767,22 @@ __device__ __forceinline__ uint32_t tok_careful(EIn& in, const HuffP& hl, const 
 // TOK_FIT_* bits), which is what BAM bodies at zlib's default levels give (profiles/
 // huffman_length_ranges/ranges.txt): the fast path then runs the shorter lookups (tok_fast_spec).
 // The careful symbol keeps the generic lookup on the unfolded tables.
-// One structured loop (no continue / goto inside): every path of an iteration joins at
+// Structured loops (no continue / goto inside): every path of an iteration joins at
 // the loop's end with an exit code, so the decoder state needs no per-path copies.
+//
+// interior (wave-uniform, SPEC only; 0 with env HBAM_TOK_INTERIOR=0): the specialised loop has a
+// second, shorter body for the iterations in which no running lane can reach an end: every one of
+// them has >= TOK_FAST_BITS stream bits left (no careful symbol, no `fast` routing) and
+// op + TOK_ITER_OUT <= isize (none of the output-full logic, tok_fast_spec<true, true>).  One ballot
+// at the top of the iteration asks that; when some running lane no longer qualifies (the last 64
+// bits of its stream, the last 260 bytes of its output) the wave goes on in the full body with the
+// same in / op / sink / it / ex and the pending packet, and comes back once every running lane
+// qualifies again (the lane that was near its end has ended, the others are mid-block).
 template <bool SPEC>
 __device__ __forceinline__ uint32_t tok_symbols(EIn& in, const HuffP& hl, const HuffP& hd,
                                                 const uint8_t* __restrict__ syms_ll,
                                                 const uint8_t* __restrict__ syms_d, TSink& sink,
-                                                uint32_t& op, uint32_t isize, uint32_t& it
+                                                uint32_t& op, uint32_t isize, uint32_t& it, uint32_t interior
 #ifdef HBAM_PROF
                                                 , uint64_t* pt, uint64_t* pc, uint64_t& tq
 #endif
@@ -756,34 +791,62 @@ __device__ __forceinline__ uint32_t tok_symbols(EIn& in, const HuffP& hl, const 
   uint32_t ex = 0;  // 0 next symbol, 1 end of block, 2 leave (zlib stops), 3 data error
   TPend pd;
   pd.clear();
-  // A wave-uniform loop (the exit is a ballot): a lane whose block has ended idles in it, as
-  // it idled at the exit of a divergent loop, without the per-iteration exec-mask bookkeeping
-  // of one.  The careful symbol (a lane's last 64 stream bits) runs behind a wave-uniform test.
-  // With the predicated match mark and the branch-free bases: Huffman 31.1 -> 30.65 ms at
-  // 5 GB, same output (profiles/r05/ab/huffman_uniform_loop_5g.txt).
+  const bool two = SPEC && interior != 0u;
+#define TOK_ANY(c) (__builtin_amdgcn_ballot_w64(c) != 0u)
+#define TOK_INNER (in.total - in.consumed >= TOK_FAST_BITS && op + TOK_ITER_OUT <= isize)
   for (;;) {
-    TOK_PC(0);
+    if (two) {
+      while (TOK_ANY(ex == 0u) && !TOK_ANY(ex == 0u && !TOK_INNER)) {
+        TOK_PC(0);
+        TOK_PC(4);  // of which in the interior body
+        TOK_ITER(2);
 #ifdef HBAM_PROF
-    TOK_PT(2);
+        TOK_PT(2);
 #endif
-    if ((__builtin_amdgcn_readfirstlane(++it) & (TOK_K - 1u)) == 0u) ein_epoch(in);
+        if ((__builtin_amdgcn_readfirstlane(++it) & (TOK_K - 1u)) == 0u) ein_epoch(in);
 #ifdef HBAM_PROF
-    TOK_PT(0);  // the epoch: merge (waits for the quad in flight) + the next request
+        TOK_PT(0);
 #endif
-    const bool run = ex == 0u && !ein_short(in, TOK_FAST_BITS);
-    const bool fast = in.total - in.consumed >= TOK_FAST_BITS;
-    if (run && fast) ex = tok_fast_spec<SPEC>(in, fl, fd, syms_ll, syms_d, sink, op, isize, pd);
-    if (__builtin_amdgcn_ballot_w64(run && !fast) != 0u) {
-      if (run && !fast) {
-        pd.flush(sink);
-        ex = tok_careful(in, hl, hd, syms_ll, syms_d, sink, op, isize);
+        if (ex == 0u && !ein_short(in, TOK_FAST_BITS))
+          ex = tok_fast_spec<SPEC, SPEC>(in, fl, fd, syms_ll, syms_d, sink, op, isize, pd);
+#ifdef HBAM_PROF
+        TOK_PT(1);
+#endif
       }
     }
+    if (!TOK_ANY(ex == 0u)) break;
+    // A wave-uniform loop (the exit is a ballot): a lane whose block has ended idles in it, as
+    // it idled at the exit of a divergent loop, without the per-iteration exec-mask bookkeeping
+    // of one.  The careful symbol (a lane's last 64 stream bits) runs behind a wave-uniform test.
+    // With the predicated match mark and the branch-free bases: Huffman 31.1 -> 30.65 ms at
+    // 5 GB, same output (profiles/r05/ab/huffman_uniform_loop_5g.txt).
+    // (with the interior body it also ends once every running lane qualifies for that again)
+    do {
+      TOK_PC(0);
+      TOK_ITER(SPEC ? 1 : 0);
 #ifdef HBAM_PROF
-    TOK_PT(1);
+      TOK_PT(2);
 #endif
-    if (__builtin_amdgcn_ballot_w64(ex == 0u) == 0u) break;
+      if ((__builtin_amdgcn_readfirstlane(++it) & (TOK_K - 1u)) == 0u) ein_epoch(in);
+#ifdef HBAM_PROF
+      TOK_PT(0);  // the epoch: merge (waits for the quad in flight) + the next request
+#endif
+      const bool run = ex == 0u && !ein_short(in, TOK_FAST_BITS);
+      const bool fast = in.total - in.consumed >= TOK_FAST_BITS;
+      if (run && fast) ex = tok_fast_spec<SPEC>(in, fl, fd, syms_ll, syms_d, sink, op, isize, pd);
+      if (__builtin_amdgcn_ballot_w64(run && !fast) != 0u) {
+        if (run && !fast) {
+          pd.flush(sink);
+          ex = tok_careful(in, hl, hd, syms_ll, syms_d, sink, op, isize);
+        }
+      }
+#ifdef HBAM_PROF
+      TOK_PT(1);
+#endif
+    } while (TOK_ANY(ex == 0u) && !(two && !TOK_ANY(ex == 0u && !TOK_INNER)));
   }
+#undef TOK_INNER
+#undef TOK_ANY
   pd.flush(sink);  // the last fast iteration's packet and mark
   return ex;
 }
@@ -791,11 +854,13 @@ __device__ __forceinline__ uint32_t tok_symbols(EIn& in, const HuffP& hl, const 
 // Inflate one raw DEFLATE stream (cdata, nbytes) to exactly isize bytes into the token sink.
 // syms_ll: 288 u8 LDS slots (symbol & 255; bit 8 from Huff.hlim); syms_d: 32 u8 LDS slots;
 // lens: LENS_SLOT bytes of 16-aligned global scratch.  tok_generic (wave-uniform): never take the
-// specialised symbol loop.  Returns INF_OK / INF_SHORT / INF_DATA.
+// specialised symbol loop; tok_interior (wave-uniform): 0 keeps the specialised loop out of its
+// interior body.  Returns INF_OK / INF_SHORT / INF_DATA.
 __device__ __forceinline__ int32_t inflate_tokens_block(const uint8_t* __restrict__ cdata, uint32_t nbytes,
                                         uint32_t isize, uint8_t* __restrict__ syms_ll,
                                         uint8_t* __restrict__ syms_d, uint8_t* __restrict__ lens,
-                                        TSink& sink, uint32_t* produced, uint32_t tok_generic
+                                        TSink& sink, uint32_t* produced, uint32_t tok_generic,
+                                        uint32_t tok_interior
 #ifdef HBAM_PROF
                                         , uint64_t* pt, uint64_t* pc
 #endif
@@ -982,9 +1047,9 @@ __device__ __forceinline__ int32_t inflate_tokens_block(const uint8_t* __restric
       const bool mine = (fit & TOK_FIT_LOW) != 0u && (fit_d & TOK_FIT_M11) != 0u;
       uint32_t ex;
 #ifdef HBAM_PROF
-#define TOK_SYMBOLS_ARGS in, hl, hd, syms_ll, syms_d, sink, op, isize, it, pt, pc, tq
+#define TOK_SYMBOLS_ARGS in, hl, hd, syms_ll, syms_d, sink, op, isize, it, tok_interior, pt, pc, tq
 #else
-#define TOK_SYMBOLS_ARGS in, hl, hd, syms_ll, syms_d, sink, op, isize, it
+#define TOK_SYMBOLS_ARGS in, hl, hd, syms_ll, syms_d, sink, op, isize, it, tok_interior
 #endif
       if (__builtin_amdgcn_ballot_w64(!mine) == 0u) {
         TOK_BODY_ENTERED(1);

@@ -15,7 +15,9 @@
 // when the "ballot", here this one lane, finds tables that fit; HBAM_TOK_GENERIC=1 in the
 // environment forces the generic one, as in the library).  The model counts the loop entries per
 // body, prints the totals, and with -v after the blocks file one line per block
-// (tests/test_tok_spec_model.py).
+// (tests/test_tok_spec_model.py).  HBAM_TOK_INTERIOR=0 keeps the specialised loop out of its interior
+// body, as in the library; -i instead of -v adds a second line per block with the loop iterations
+// per body (tests/test_tok_interior_model.py).
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -24,6 +26,8 @@
 #ifdef HBAM_MODEL_BODIES  // the source has tok_symbols (not the r02 one)
 static uint64_t g_body_entries[2];  // [0] generic, [1] specialised
 #define TOK_BODY_ENTERED(v) (++g_body_entries[v])
+static uint64_t g_body_iters[3];  // [0] generic, [1] specialised, [2] specialised, interior body
+#define TOK_ITER(v) (++g_body_iters[v])
 #endif
 #include "inflate_tok.h"
 
@@ -57,11 +61,14 @@ int main(int argc, char** argv) {
     return 2;
   }
   const uint32_t n = hdr[1];
-  const bool verbose = argc > 2 && strcmp(argv[2], "-v") == 0;
+  const bool iters = argc > 2 && strcmp(argv[2], "-i") == 0;
+  const bool verbose = iters || (argc > 2 && strcmp(argv[2], "-v") == 0);
 #ifdef HBAM_MODEL_BODIES
   const char* tg = getenv("HBAM_TOK_GENERIC");
   const uint32_t tok_generic = tg && strtol(tg, nullptr, 10) != 0 ? 1u : 0u;
-  uint64_t entries[2] = {0, 0};
+  const char* ti = getenv("HBAM_TOK_INTERIOR");
+  const uint32_t tok_interior = ti && strtol(ti, nullptr, 10) == 0 ? 0u : 1u;
+  uint64_t entries[2] = {0, 0}, its[3] = {0, 0, 0};
 #endif
   uint32_t bad = 0, short_ = 0, data = 0;
   uint64_t ubytes = 0;
@@ -97,7 +104,7 @@ int main(int argc, char** argv) {
 #endif
     const int32_t rc = inflate_tokens_block(cbuf + a, clen, isize, syms_ll, syms_d, lens, sink, &produced
 #ifdef HBAM_MODEL_BODIES
-                                            , tok_generic
+                                            , tok_generic, tok_interior
 #endif
 #ifdef HBAM_PROF
                                             , pt, pc
@@ -154,6 +161,14 @@ int main(int argc, char** argv) {
       entries[1] = g_body_entries[1];
 #endif
       printf("\n");
+#ifdef HBAM_MODEL_BODIES
+      if (iters) {
+        printf("iterations %u generic %llu specialised %llu interior %llu\n", b,
+               (unsigned long long)(g_body_iters[0] - its[0]), (unsigned long long)(g_body_iters[1] - its[1]),
+               (unsigned long long)(g_body_iters[2] - its[2]));
+        for (int q = 0; q < 3; ++q) its[q] = g_body_iters[q];
+      }
+#endif
     }
     free(cbuf);
     free(expect);
@@ -169,6 +184,10 @@ int main(int argc, char** argv) {
 #ifdef HBAM_MODEL_BODIES
   printf("symbol loop entries: generic %llu specialised %llu\n", (unsigned long long)g_body_entries[0],
          (unsigned long long)g_body_entries[1]);
+  if (iters)
+    printf("symbol loop iterations: generic %llu specialised %llu interior %llu\n",
+           (unsigned long long)g_body_iters[0], (unsigned long long)g_body_iters[1],
+           (unsigned long long)g_body_iters[2]);
 #endif
   return bad ? 1 : 0;
 }

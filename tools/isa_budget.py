@@ -14,7 +14,9 @@ the token logic of the iteration itself (tok_fast_spec, ein_drop, ein_peek), the
 (tok_careful) and the loop's exit bookkeeping (tok_symbols / inflate_tokens_block).  The fast path
 is the straight run of blocks from the loop head to the back edge that holds no tok_careful line;
 blocks with tok_careful lines are the careful symbol, and the short side blocks hold the chunk /
-window stores.  Counts by category, nothing else.
+window stores.  Below each table: the straight-line iteration (straight_line), the labelled blocks
+a wave runs when no lane takes the careful symbol and no store side block is entered.  Counts by
+category, nothing else.
 """
 import re
 import sys
@@ -73,6 +75,7 @@ def main():
     # instructions with their block label and attributed function
     ins, label, cur = [], "entry", ("?", 0)
     labels = {}
+    falls = set()  # where an unlabelled block (; %bb.N:) begins: the fall-through of a branch
     for l in body:
         t = l.strip()
         m = re.match(r"^(\.LBB\w+):", t)
@@ -84,6 +87,8 @@ def main():
         if m:
             cur = (files.get(m.group(1), "?"), int(m.group(2)))
             continue
+        if re.match(r"^; %bb\.\d+:", t):
+            falls.add(len(ins))
         if not t or t.startswith((".", ";", "//")) or t.endswith(":"):
             continue
         op = t.split()[0]
@@ -132,7 +137,84 @@ def main():
             for u, v in zip(("VALU", "SALU", "LDS", "VMEM", "other"), row):
                 tot[u] = tot.get(u, 0) + v
         print("    %-12s %5d %5d %5d %5d %5d" % ("total", tot["VALU"], tot["SALU"], tot["LDS"], tot["VMEM"], tot["other"]))
+        straight_line(ins, labels, falls, a, k)
         print()
+
+
+def straight_line(ins, labels, falls, a, k):
+    """The iteration a wave runs when no lane takes the careful symbol and no store side block is
+    entered, in whole labelled blocks from the loop head to the back edge.  A block is followed by
+    the next labelled block, with two exceptions.  A block that holds a store and that a conditional
+    branch of the block before it skips exactly (the branch targets the label after it) is a side
+    block: the walk takes the branch.  A block with a conditional branch over tok_careful lines is
+    the careful-symbol gate: the walk takes that branch and counts nothing of the gate's block.  The
+    "fast path" above also counts what sits behind the gate without a tok_careful line (the pending
+    packet's flush, its refill, TSink::match, exec-restore stubs); this walk does not.  The epoch
+    blocks, which run every TOK_K-th iteration, are on the walk, and so is store code that shares a
+    label with the straight path: a guarded store tail, the unlabelled fall-through of an
+    s_cbranch_execz that skips fewer than 40 instructions with a store among them.  A labelled
+    block the table calls a side block can therefore be on the walk (straight code that ends in
+    such a tail).  The tails on the walk are counted on their own line, so that two trees are
+    compared without them."""
+    starts = sorted(v for v in set(labels.values()) if a <= v <= k)
+    if not starts or starts[0] != a:
+        starts = [a] + starts
+    bounds = {s0: (starts[i + 1] if i + 1 < len(starts) else k + 1) for i, s0 in enumerate(starts)}
+
+    def branches(s0):
+        for i in range(s0, bounds[s0]):
+            m = re.match(r"s_cbranch\w*\s+(\.LBB\w+)", ins[i][3])
+            if m and m.group(1) in labels:
+                yield i, labels[m.group(1)]
+
+    def skipped(src, n):  # n: a store side block that src branches around
+        stores = any(y[1].startswith(("global_store", "scratch_store")) for y in ins[n:bounds[n]])
+        return stores and any(t == bounds[n] for _, t in branches(src))
+
+    def gate(n):  # the target of n's branch over the careful symbol
+        for i, t in branches(n):
+            if i < t <= k and any(y[2] == "careful" for y in ins[i + 1:t]):
+                return t
+        return None
+
+    path, visited, cur, walked = [], [], a, set()
+    while True:
+        path += ins[cur:bounds[cur]]
+        walked.update(range(cur, bounds[cur]))
+        visited.append(ins[cur][0])
+        if bounds[cur] > k:
+            break
+        nxt = bounds[cur]
+        for _ in range(len(starts)):
+            if skipped(cur, nxt):
+                nxt = bounds[nxt]
+            elif gate(nxt) is not None:
+                nxt = gate(nxt)
+            else:
+                break
+        if any(y[2] == "careful" for y in ins[nxt:bounds[nxt]]):
+            print("  straight-line iteration: the walk ran into the careful symbol at %s" % ins[nxt][0])
+            return
+        cur = nxt
+    u = {n: sum(1 for y in path if unit(y[1]) == n) for n in ("VALU", "SALU", "LDS", "VMEM", "other")}
+    print("  straight-line iteration (no careful symbol, no store side block): %d instructions: %d VALU, %d SALU, "
+          "%d LDS, %d VMEM, %d other" % (len(path), u["VALU"], u["SALU"], u["LDS"], u["VMEM"], u["other"]))
+    print("    blocks: %s" % " ".join(visited))
+    tails = set()
+    for i in sorted(walked):
+        m = re.match(r"s_cbranch_execz\s+(\.LBB\w+)", ins[i][3])
+        t = labels.get(m.group(1), -1) if m else -1
+        if i + 1 in falls and i + 1 < t <= k + 1 and t - (i + 1) < 40 and any(
+                y[1].startswith(("global_store", "scratch_store")) for y in ins[i + 1:t]):
+            tails.update(range(i + 1, t))
+    tails &= walked
+    print("    of which in guarded store tails (skipped when no lane stores): %d; without them: %d instructions"
+          % (len(tails), len(path) - len(tails)))
+    print("    %-12s %5s %5s %5s %5s %5s" % ("", "VALU", "SALU", "LDS", "VMEM", "other"))
+    for c in [c for c, _ in CATS] + ["other"]:
+        row = [sum(1 for y in path if y[2] == c and unit(y[1]) == n) for n in ("VALU", "SALU", "LDS", "VMEM", "other")]
+        if sum(row):
+            print("    %-12s %5d %5d %5d %5d %5d" % ((c,) + tuple(row)))
 
 
 if __name__ == "__main__":

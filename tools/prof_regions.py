@@ -3,7 +3,8 @@
 inflate: one hbam_decode_split over a synthetic BAM; per BGZF block the Huffman pass adds its
   cycles per region (slots 16..23 of 32 per block) and counts (24..27):
   regions 0 epoch/stall, 1 lit/len lookup, 2 literal, 3 length extra + refill, 4 distance,
-  5 match emit, 6 header/tables, 7 slow path; counts 0 symbols, 1 stalls, 2 slow symbols.
+  5 match emit, 6 header/tables, 7 slow path; counts (24..28) 0 the wave's symbol-loop iterations the
+  lane sat through, 1..3 the decoder's state at exit, 4 those of slot 0 that ran in the interior body.
 guess: one hbam_guess_batch of --guesses random offsets; per guess 8 slots:
   0 whole guess, 1 BGZF candidate search, 2 BAM candidate search, 3 record chain decode,
   4 BGZF candidates tried, 5 BAM candidates tried, 6 records decoded, 7 listed magics."""
@@ -69,6 +70,20 @@ def main():
         print("  symbols/block %.0f, cycles/symbol %.1f, stalls/symbol %.3f, slow/symbol %.4f"
               % (sym / nb, tot / max(sym, 1), stall / max(sym, 1), slow / max(sym, 1)))
         print("  block cycles:", pct(R.sum(1)))
+        # every lane of a wave counts each of the wave's iterations, whichever lanes still run, so
+        # the sums weigh a wave's iterations by the lanes that entered that symbol loop
+        its, inner = P[:, 24], P[:, 28]
+        lane = its > 0
+        print("  wave iterations in the interior body: %.0f of %.0f, %.2f%% (per lane: p1 %.2f%% p50 %.2f%% min %.2f%%; "
+              "%d of %d blocks in the lane pass)" % (inner.sum(), its.sum(), 100 * inner.sum() / max(its.sum(), 1),
+              100 * np.percentile(inner[lane] / its[lane], 1), 100 * np.percentile(inner[lane] / its[lane], 50),
+              100 * (inner[lane] / its[lane]).min(), lane.sum(), nb))
+        if lane.all():  # every block in the lane pass, in order (HBAM_WAVE_MAX_BLOCKS=0): a wave is 64 blocks in a row
+            nw = nb // 64
+            w = np.argmax(its[:nw * 64].reshape(nw, 64), 1) + 64 * np.arange(nw)  # the lane that ran longest
+            print("  per wave (%d waves, its longest lane): %.0f of %.0f iterations interior, %.2f%%; wave p1 %.2f%% min %.2f%%"
+                  % (nw, inner[w].sum(), its[w].sum(), 100 * inner[w].sum() / its[w].sum(),
+                     100 * np.percentile(inner[w] / its[w], 1), 100 * (inner[w] / its[w]).min()))
         # LZ77 pass (k_resolve): slots 2 total, 3 setup, 4 descriptors, 5 ordered rounds,
         # 12 pre matches, 13 write-back + slide; 6 rounds, 7 matches
         Q = P[:, [2, 3, 4, 12, 5, 13]]
