@@ -198,6 +198,17 @@ enum BufId {
   B_OV_KEEP,
   B_OV_CNT,
   B_OV_OFF,
+  // text VCF (hbam_vcf.hip)
+  B_VCF_NL,
+  B_VCF_TAB,
+  B_VCF_CNT,
+  B_VCF_OFF,
+  B_VCF_STARTS,
+  B_VCF_COLS,
+  B_VCF_SMALL,
+  B_VCF_TABLE,
+  B_VCF_NAMES,
+  B_VCF_REL,
   B_COUNT_ALL
 };
 
@@ -2662,3 +2673,4 @@ extern "C" int64_t hbam_bgzf_compress(hbam_ctx* c, const uint8_t* src, int src_o
 #include "hbam_bcf_api.hip"
 #include "hbam_comm.hip"
 #include "hbam_bai.hip"
+#include "hbam_vcf.hip"

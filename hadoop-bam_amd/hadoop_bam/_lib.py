@@ -62,6 +62,7 @@ EXPORTS = [
     "hbam_comm_destroy", "hbam_comm_split_points", "hbam_sort_exchange", "hbam_split_open_reader",
     "hbam_split_read_bytes", "hbam_rewrite_groups", "hbam_records_to_host", "hbam_split_records_to_host",
     "hbam_bai_bound", "hbam_bai_build", "hbam_overlap_filter",
+    "hbam_vcf_decode_split", "hbam_vcf_columns_to_host", "hbam_vcf_release", "hbam_vcf_gather_lines",
 ]
 
 # hbam_read_fn: int64_t read(void* user, uint64_t offset, uint64_t len, uint8_t* dst)
@@ -151,6 +152,23 @@ class BcfColumnsC(C.Structure):
 BCF_FIELDS = [("rel", np.int64), ("rec_off", np.uint64), ("key", np.int64), ("l_shared", np.int32),
               ("l_indiv", np.int32), ("chrom", np.int32), ("pos", np.int32), ("rlen", np.int32),
               ("qual", np.uint32), ("n_allele_info", np.int32), ("n_fmt_sample", np.int32)]
+
+
+class VcfContigC(C.Structure):
+    _fields_ = [("name_off", C.c_uint32), ("name_len", C.c_uint32), ("ordinal", C.c_int32)]
+
+
+class VcfColumnsC(C.Structure):
+    _fields_ = [
+        ("n", C.c_uint64), ("status", C.c_int32), ("host", C.c_int32), ("line_off", C.c_void_p),
+        ("line_len", C.c_void_p), ("tab", C.c_void_p), ("chrom", C.c_void_p), ("pos", C.c_void_p),
+        ("ref_len", C.c_void_p), ("key", C.c_void_p), ("text", C.c_void_p), ("text_base", C.c_uint64),
+        ("text_len", C.c_uint64),
+    ]
+
+
+VCF_FIELDS = [("line_off", np.uint64), ("line_len", np.uint32), ("chrom", np.int32), ("pos", np.int32),
+              ("ref_len", np.int32), ("key", np.int64)]
 
 
 FIXED = [("voffset", np.uint64), ("key", np.int64), ("rec_off", np.uint64),
@@ -258,6 +276,13 @@ def load(path=None):
                                        C.POINTER(C.c_uint64)]),
         "hbam_overlap_filter": (C.c_int64, [vp, C.POINTER(Columns), C.c_int32, C.c_int64, C.c_int64,
                                             C.c_int32, vp]),
+        "hbam_vcf_decode_split": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+                                            C.c_uint64, C.c_uint64, vp, C.c_uint32, vp, C.c_uint64, C.c_int32,
+                                            C.POINTER(VcfColumnsC)]),
+        "hbam_vcf_columns_to_host": (C.c_int, [vp, C.POINTER(VcfColumnsC), C.POINTER(VcfColumnsC)]),
+        "hbam_vcf_release": (None, [vp, C.POINTER(VcfColumnsC)]),
+        "hbam_vcf_gather_lines": (C.c_int, [vp, C.POINTER(VcfColumnsC), vp, C.c_uint64, vp, C.c_uint64, vp,
+                                            C.POINTER(C.c_uint64)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name, None)
@@ -898,3 +923,100 @@ class Context:
             out["data"] = self._d2h(d.data, int(d.data_len), np.uint8)
         out["timing"] = self.timing()
         return out
+
+    # ---- text VCF (hbam_vcf.hip) ------------------------------------------------------------------
+    @staticmethod
+    def vcf_contig_table(contigs):
+        """The contig dictionary as hbam_vcf_decode_split takes it: (VcfContigC array, size, names
+        bytes).  `contigs` = the ##contig IDs in header order (bytes); a later duplicate overwrites
+        the earlier one's ordinal.  Open addressing, linear probing, FNV-1a, a power of two of at
+        least twice the distinct IDs."""
+        d = {}
+        for i, name in enumerate(contigs):
+            d[bytes(name)] = i
+        size = 2
+        while size < 2 * len(d):
+            size *= 2
+        tab = (VcfContigC * size)()
+        for e in tab:
+            e.ordinal = -1
+        names = bytearray()
+        for name, ordinal in d.items():
+            h = 2166136261
+            for b in name:
+                h = ((h ^ b) * 16777619) & 0xffffffff
+            h &= size - 1
+            while tab[h].ordinal >= 0:
+                h = (h + 1) & (size - 1)
+            tab[h].name_off, tab[h].name_len, tab[h].ordinal = len(names), len(name), ordinal
+            names += name
+        return tab, size, bytes(names)
+
+    def vcf_decode_split_device(self, data, start, length, data_start, table, text_base=0, file_len=None,
+                                keep_text=False):
+        """hbam_vcf_decode_split -> (rc, device VcfColumnsC); `table` = vcf_contig_table(...)."""
+        p, n, dev, keep = self._ptr(data)
+        if file_len is None:
+            file_len = text_base + n
+        tab, size, names = table
+        nm = np.frombuffer(names, np.uint8) if names else np.zeros(1, np.uint8)
+        d = VcfColumnsC()
+        rc = self.L.hbam_vcf_decode_split(self.h, p, dev, int(text_base), n, int(file_len), int(start), int(length),
+                                          int(data_start), C.cast(tab, C.c_void_p), size,
+                                          C.c_void_p(nm.ctypes.data), len(names), int(bool(keep_text)), C.byref(d))
+        return rc, d
+
+    def vcf_decode_split(self, data, start, length, data_start, table, text_base=0, file_len=None):
+        """VCFRecordReader over one split (hbam_vcf_decode_split + hbam_vcf_columns_to_host) -> host
+        numpy columns."""
+        rc, d = self.vcf_decode_split_device(data, start, length, data_start, table, text_base, file_len)
+        if rc:
+            return {"rc": rc, "error": self.last_error()}
+        h = VcfColumnsC()
+        rc = self.L.hbam_vcf_columns_to_host(self.h, C.byref(d), C.byref(h))
+        if rc:
+            return {"rc": rc, "error": self.last_error()}
+        k = int(h.n)
+        out = {"rc": 0, "n": k, "status": int(h.status)}
+
+        def arr(ptr, count, dt):
+            if not count:
+                return np.zeros(0, dt)
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)),
+                                         shape=(count * np.dtype(dt).itemsize,)).view(dt).copy()
+        for name, dt in VCF_FIELDS:
+            out[name] = arr(getattr(h, name), k, dt)
+        out["tab"] = arr(h.tab, 8 * k, np.uint32).reshape(k, 8)
+        self.L.hbam_vcf_release(self.h, C.byref(h))
+        out["timing"] = self.timing()
+        return out
+
+    def vcf_gather_lines(self, dcols, perm=None, n=None):
+        """hbam_vcf_gather_lines over the device columns of a keep_text decode: lines perm[0..n)
+        (a device pointer, or None for the identity), each followed by a newline -> host bytes."""
+        n = int(dcols.n) if n is None else int(n)
+        if n == 0:
+            return b""
+        vp = C.c_void_p
+        bufs = []
+
+        def alloc(nbytes):
+            b = vp()
+            rc = self.L.hbam_device_alloc(self.h, int(nbytes), C.byref(b))
+            if rc:
+                raise RuntimeError("hbam_device_alloc failed (%d): %s" % (rc, self.last_error()))
+            bufs.append(b)
+            return b
+        try:
+            off = alloc(8 * (n + 1))
+            tot = C.c_uint64(0)
+            rc = self.L.hbam_vcf_gather_lines(self.h, C.byref(dcols), perm, n, None, 0, off, C.byref(tot))
+            if not rc:
+                pay = alloc(max(int(tot.value), 1))
+                rc = self.L.hbam_vcf_gather_lines(self.h, C.byref(dcols), perm, n, pay, tot.value, off, C.byref(tot))
+            if rc:
+                raise RuntimeError("hbam_vcf_gather_lines failed (%d): %s" % (rc, self.last_error()))
+            return self._d2h(pay.value, int(tot.value), np.uint8).tobytes()
+        finally:
+            for b in bufs:
+                self.L.hbam_device_free(self.h, b)

@@ -168,11 +168,29 @@ class BCFRecordReader:
 
 
 class VCFInputFormat:
-    """The BCF half of VCFInputFormat.java:197-310: FileInputFormat splits of each BCF path are
-    re-aligned to records by the guesser (addGuessedSplits :248-310)."""
+    """VCFInputFormat.java:124-310: FileInputFormat splits of each BCF path are re-aligned to
+    records by the guesser (addGuessedSplits :248-310); those of a text VCF path stay as they are
+    and are read by vcf.VCFRecordReader.  A path whose format is unknown takes the BCF route (and
+    fails on its header there)."""
+
+    def getFormat(self, path, conf=None, data=None):
+        """VCFInputFormat.getFormat (:124-150): by extension when hadoopbam.vcf.trust-exts is set
+        (the default), else (or for another extension) by the file's first byte; None: unknown."""
+        from .vcf import TRUST_EXTS_PROPERTY, VCFFormat
+        trust = str((conf or {}).get(TRUST_EXTS_PROPERTY, "true")).lower() == "true"
+        if trust:
+            f = VCFFormat.inferFromFilePath(path)
+            if f is not None:
+                return f
+        try:
+            return VCFFormat.inferFromData(data if data is not None else path)
+        except (IOException, OSError):
+            return None
 
     def getSplits(self, path, split_size, conf=None, data=None):
         ss = SeekableFile(data if data is not None else path)
+        if self.getFormat(path, conf, ss) == "VCF":
+            return compute_file_splits(path, ss.length, split_size)
         g = BCFSplitGuesser(ss, conf=conf)
         bg = g.isBGZF()
         out = []
@@ -194,7 +212,11 @@ class VCFInputFormat:
         return out
 
     def createRecordReader(self, split, conf=None, data=None):
-        rr = BCFRecordReader()
+        if self.getFormat(split.getPath(), conf, data) == "VCF":
+            from .vcf import VCFRecordReader
+            rr = VCFRecordReader()
+        else:
+            rr = BCFRecordReader()
         rr.initialize(split, conf, data)
         return rr
 

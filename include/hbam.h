@@ -15,8 +15,9 @@
  *   HBAM_EREFID       IllegalArgumentException (reference index not in dictionary)
  *   HBAM_EDATA        RuntimeException(java.util.zip.DataFormatException)
  *   HBAM_EINDEX       IndexOutOfBoundsException
- *   HBAM_ETRIBBLE     htsjdk TribbleException (BCF)
- *   HBAM_ERUNTIME     another RuntimeException out of BCF2Codec.decode (BCF, unpinned)
+ *   HBAM_ETRIBBLE     htsjdk TribbleException (BCF, text VCF)
+ *   HBAM_ERUNTIME     another RuntimeException out of BCF2Codec.decode (BCF, unpinned); the
+ *                     NullPointerException after VCFCodec.decode returns null (text VCF)
  *   HBAM_ENULL        NullPointerException (multi-input Sort's group rewrite, cli/Utils.java:316-323)
  *   HBAM_ECLASSCAST   ClassCastException (an RG / PG attribute that is not a string)
  *
@@ -570,6 +571,89 @@ int hbam_guess_bcf_windows(hbam_ctx* ctx, const uint8_t* windows, int on_device,
 int hbam_bcf_decode_split(hbam_ctx* ctx, const uint8_t* comp, int on_device, uint64_t comp_base,
                           uint64_t comp_len, uint64_t file_len, const hbam_bcf_header* h, uint64_t v_start,
                           uint64_t v_end, hbam_bcf_columns* out);
+
+/* ---- text VCF: VCFRecordReader (VCFRecordReader.java:72-142), the VCF half of VCFInputFormat
+ * (VCFInputFormat.java:124-223) and the vcf-sort plugin (cli/plugins/VCFSort.java) ------------
+ * htsjdk (AsciiLineReader, AsciiLineReaderIterator, VCFCodec) is not in the reference tree: the
+ * line and decode rules are restated from memory, parity unpinned (DESIGN.md lists them).
+ * Lines: a line ends at '\n'; a '\r' directly before it is not part of the line; a last line
+ * without '\n' is a line; a file ending in '\n' has no empty last line; a lone '\r' is not a line
+ * end here.  The header (the '#' lines through #CHROM) is parsed by the host: it passes
+ * data_start (the offset of the line after #CHROM) and the contig dictionary. */
+
+/* One slot of the contig dictionary (header.getContigLines(): ID -> ordinal, a later duplicate
+ * ID overwriting the earlier one): an open-addressing table with linear probing, size a power of
+ * two and at least twice the number of contigs, slot of a name = FNV-1a (32-bit, offset basis
+ * 2166136261, prime 16777619) over its bytes & (size - 1).  ordinal < 0 marks an empty slot. */
+typedef struct hbam_vcf_contig {
+  uint32_t name_off;  /* the ID's bytes: names[name_off, name_off + name_len) */
+  uint32_t name_len;
+  int32_t ordinal;
+} hbam_vcf_contig;
+
+/* VCFRecordReader output of one split.  After hbam_vcf_decode_split every pointer is device memory
+ * owned by the context, valid until the next hbam_vcf_decode_split on it (host = 0); after
+ * hbam_vcf_columns_to_host they are host arrays owned by the caller (host = 1, text = NULL), freed
+ * by hbam_vcf_release.  Line i is file bytes [line_off[i], line_off[i] + line_len[i]): the raw
+ * line a Java caller hands to VCFCodec (VariantContextWritable's value). */
+typedef struct hbam_vcf_columns {
+  uint64_t n;          /* lines returned before `status` */
+  int32_t status;      /* HBAM_OK, the exception nextKeyValue() raises after n lines, or HBAM_EMORE */
+  int32_t host;
+  uint64_t* line_off;  /* file offset of the line's first byte */
+  uint32_t* line_len;  /* without the '\n' and a '\r' before it */
+  uint32_t* tab;       /* 8 per line, relative to the line start: the ends of CHROM, POS, ID, REF, ALT,
+                          QUAL, FILTER and INFO (the 8th is line_len when the line has no FORMAT) */
+  int32_t* chrom;      /* contigDict ordinal of CHROM, or (int)MurmurHash3.murmurhash3(CHROM, 0) */
+  int32_t* pos;        /* POS as written (1-based) */
+  int32_t* ref_len;    /* bytes of REF */
+  int64_t* key;        /* (long)chrom << 32 | (long)(pos - 1): the low half sign-extends, POS 0 -> -1 */
+  uint8_t* text;       /* the window on the device (keep_text != 0), else NULL */
+  uint64_t text_base;  /* file offset of text[0] */
+  uint64_t text_len;
+} hbam_vcf_columns;
+
+/* VCFRecordReader.initialize + the nextKeyValue loop over FileSplit [start, start + length) of an
+ * uncompressed VCF file of file_len bytes.  text = file bytes [text_base, text_base + text_len), a
+ * window of at most 2 GiB (HBAM_EINVAL above; line offsets inside a window are 32-bit) that begins at
+ * or before the reader's first byte: data_start for start == 0, else start - 1.  A device-resident
+ * window that does not begin on a 16-byte boundary is read from the boundary below it (the up to 15
+ * bytes before `text` must be readable, as they are inside any allocation).
+ * start == 0: the lines from data_start on are candidates, positions counted from 0 (the caller has
+ * raised "Empty VCF file" when there is none, :112-116).  start != 0: the reader is opened at
+ * start - 1, everything through the first '\n' at or after it is discarded (:103-105) and positions
+ * count from start - 1.  A candidate line is returned while one exists and its position < length
+ * (:129): with start != 0 a line beginning exactly at start + length - 1 is read by no split (the
+ * next one discards it); the reference's behaviour, kept.
+ * Per returned line, the first failure ends the split with out->status, out->n = the lines before it:
+ *   HBAM_ERUNTIME  the line begins with '#' (VCFCodec.decode returns null: NullPointerException; only
+ *                  a split with start != 0 inside the header sees one);
+ *   HBAM_ETRIBBLE  fewer than 8 tab-separated fields (an empty line too), or a POS that is not an
+ *                  optional single '+' / '-' and one or more ASCII digits inside int32.
+ * htsjdk's other validations (ID, alleles, FILTER, INFO, genotypes) are not restated.  CHROM bytes
+ * are taken as UTF-16 code units of equal value.  table (host, table_size slots) and names (host,
+ * names_len bytes) are the contig dictionary, copied to the device by the call.
+ * out->status = HBAM_EMORE: the window ends inside the last line the split would return (or before
+ * any line and before the split's bound) and before file_len; call again with a longer window.
+ * Work per line is bounded by its 8th tab (by its end when it has fewer): the sample columns are
+ * only read by the structural pass.  Timing: scan_ms = structural pass, walk_ms = line scan and
+ * scatter, decode_ms = field pass, total_ms, ubuf_bytes = text_len, n_records = n. */
+int hbam_vcf_decode_split(hbam_ctx* ctx, const uint8_t* text, int on_device, uint64_t text_base,
+                          uint64_t text_len, uint64_t file_len, uint64_t start, uint64_t length,
+                          uint64_t data_start, const hbam_vcf_contig* table, uint32_t table_size,
+                          const uint8_t* names, uint64_t names_len, int32_t keep_text,
+                          hbam_vcf_columns* out);
+/* host copy of the n lines' columns (not the text: the caller holds the window) */
+int hbam_vcf_columns_to_host(hbam_ctx* ctx, const hbam_vcf_columns* dev, hbam_vcf_columns* host);
+/* frees a host copy's arrays; clears the struct either way */
+void hbam_vcf_release(hbam_ctx* ctx, hbam_vcf_columns* cols);
+/* The line writer of vcf-sort: lines perm[0..n) (device u32 indices into dv's lines, each below
+ * dv->n, e.g. hbam_sort_keys' permutation of dv->key; NULL = identity) of a decode with keep_text, each
+ * followed by '\n' ("\r\n" input comes out as "\n"), packed into out (device); out_off (device,
+ * u64[n+1]) gets the exclusive scan of the lengths + 1.  out == NULL: size query (total_bytes
+ * only), as hbam_gather_records.  Timing: pools_ms, pool_bytes. */
+int hbam_vcf_gather_lines(hbam_ctx* ctx, const hbam_vcf_columns* dv, const uint32_t* perm, uint64_t n,
+                          uint8_t* out, uint64_t out_cap, uint64_t* out_off, uint64_t* total_bytes);
 
 #ifdef __cplusplus
 }
