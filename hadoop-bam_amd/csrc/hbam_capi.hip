@@ -209,6 +209,10 @@ enum BufId {
   B_VCF_TABLE,
   B_VCF_NAMES,
   B_VCF_REL,
+  // SAM text (hbam_sam.hip)
+  B_SAM_RSIZE,
+  B_SAM_STATUS,
+  B_SAM_DESC,
   B_COUNT_ALL
 };
 
@@ -2674,3 +2678,4 @@ extern "C" int64_t hbam_bgzf_compress(hbam_ctx* c, const uint8_t* src, int src_o
 #include "hbam_comm.hip"
 #include "hbam_bai.hip"
 #include "hbam_vcf.hip"
+#include "hbam_sam.hip"

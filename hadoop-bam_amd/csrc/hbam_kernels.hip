@@ -611,15 +611,16 @@ static __device__ __forceinline__ uint64_t fmix64(uint64_t k) {
 static __device__ __forceinline__ uint64_t ld_u64_unaligned(const uint8_t* p) {
   return (uint64_t)ld_u32_unaligned(p) | (uint64_t)ld_u32_unaligned(p + 4) << 32;
 }
-// MurmurHash3.murmurhash3(byte[], seed=0) incl. the h2 quirk of MurmurHash3.java:59
+// MurmurHash3.murmurhash3(byte[], seed) incl. the h2 quirk of MurmurHash3.java:59; h1 = h2 =
+// (long)seed, sign-extended (:35-36)
 // The 16-byte blocks are loaded MH_BATCH at a time, all loads of a batch in flight together,
 // and the tail as two 8-byte loads (masked): an unmapped read's hash (the whole variable part,
 // ~19 blocks) used to wait for one dependent load pair per block plus one per tail byte, and
 // with ~1 % unmapped reads about half of the waves carried one such lane.
 constexpr int32_t MH_BATCH = 8;  // 16-byte blocks of a murmur hash loaded together
-static __device__ uint64_t murmur3_java(const uint8_t* __restrict__ key, int32_t len) {
+static __device__ uint64_t murmur3_java(const uint8_t* __restrict__ key, int32_t len, int32_t seed = 0) {
   const int32_t nblocks = len / 16;
-  uint64_t h1 = 0, h2 = 0;
+  uint64_t h1 = (uint64_t)(int64_t)seed, h2 = h1;
   const uint64_t c1 = 0x87c37b91114253d5ULL, c2 = 0x4cf5ad432745937fULL;
   for (int32_t i0 = 0; i0 < nblocks; i0 += MH_BATCH) {
     uint64_t kk[2 * MH_BATCH];

@@ -120,11 +120,11 @@ __device__ __forceinline__ uint64_t vcf_fmix(uint64_t k) {
   return k ^ k >> 33;
 }
 // util/MurmurHash3.java:108-171 over a CharSequence whose UTF-16 code units are the n bytes at c,
-// seed 0.  Both quirks of the reference are kept: the block step rotates h2 as
+// h1 = h2 = (long)seed (sign-extended).  Both quirks of the reference are kept: the block step rotates h2 as
 // h2 << 31 | h1 >>> 33 (:139), and the tail (n & 7) reads charAt(0..6), the START of the string.
-__device__ int64_t murmur3_java_chars(const uint8_t* c, uint32_t n) {
+__device__ int64_t murmur3_java_chars(const uint8_t* c, uint32_t n, int32_t seed = 0) {
   const uint64_t c1 = 0x87c37b91114253d5ull, c2 = 0x4cf5ad432745937full;
-  uint64_t h1 = 0, h2 = 0;
+  uint64_t h1 = (uint64_t)(int64_t)seed, h2 = h1;
   for (uint32_t i = 0; i + 8 <= n; i += 8) {
     uint64_t k1 = (uint64_t)c[i] | (uint64_t)c[i + 1] << 16 | (uint64_t)c[i + 2] << 32 | (uint64_t)c[i + 3] << 48;
     uint64_t k2 = (uint64_t)c[i + 4] | (uint64_t)c[i + 5] << 16 | (uint64_t)c[i + 6] << 32 | (uint64_t)c[i + 7] << 48;

@@ -16,3 +16,5 @@ from .output import (  # noqa: F401
     BAMRecordWriter, KeyIgnoringBAMOutputFormat, KeyIgnoringBAMRecordWriter, SAMFileHeader,
     SAMOutputPreparer, merge_sam_into, read_sam_header)
 from .index import BAMIndex, BAMIndexer, IndexedBAMReader, parse_region  # noqa: F401
+from .sam import (  # noqa: F401
+    SAMFormat, SAMInputFormat, SAMRecordReader, SAMUnsupportedException, read_sam_text_header)

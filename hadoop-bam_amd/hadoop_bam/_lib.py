@@ -63,6 +63,7 @@ EXPORTS = [
     "hbam_split_read_bytes", "hbam_rewrite_groups", "hbam_records_to_host", "hbam_split_records_to_host",
     "hbam_bai_bound", "hbam_bai_build", "hbam_overlap_filter",
     "hbam_vcf_decode_split", "hbam_vcf_columns_to_host", "hbam_vcf_release", "hbam_vcf_gather_lines",
+    "hbam_sam_decode_split",
 ]
 
 # hbam_read_fn: int64_t read(void* user, uint64_t offset, uint64_t len, uint8_t* dst)
@@ -283,6 +284,9 @@ def load(path=None):
         "hbam_vcf_release": (None, [vp, C.POINTER(VcfColumnsC)]),
         "hbam_vcf_gather_lines": (C.c_int, [vp, C.POINTER(VcfColumnsC), vp, C.c_uint64, vp, C.c_uint64, vp,
                                             C.POINTER(C.c_uint64)]),
+        "hbam_sam_decode_split": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+                                            C.c_uint64, C.c_uint64, vp, C.c_uint32, vp, C.c_uint64, C.c_int32,
+                                            C.POINTER(Columns)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name, None)
@@ -988,6 +992,37 @@ class Context:
             out[name] = arr(getattr(h, name), k, dt)
         out["tab"] = arr(h.tab, 8 * k, np.uint32).reshape(k, 8)
         self.L.hbam_vcf_release(self.h, C.byref(h))
+        out["timing"] = self.timing()
+        return out
+
+    # ---- SAM text (hbam_sam.hip) ------------------------------------------------------------------
+    def sam_decode_split_device(self, data, start, length, data_start, table, n_ref, text_base=0, file_len=None):
+        """hbam_sam_decode_split -> (rc, device Columns), as decode_split_device; `table` =
+        vcf_contig_table(the @SQ SN names in header order)."""
+        p, n, dev, keep = self._ptr(data)
+        if file_len is None:
+            file_len = text_base + n
+        tab, size, names = table
+        nm = np.frombuffer(names, np.uint8) if names else np.zeros(1, np.uint8)
+        d = Columns()
+        rc = self.L.hbam_sam_decode_split(self.h, p, dev, int(text_base), n, int(file_len), int(start), int(length),
+                                          int(data_start), C.cast(tab, C.c_void_p), size,
+                                          C.c_void_p(nm.ctypes.data), len(names), int(n_ref), C.byref(d))
+        return rc, d
+
+    def sam_decode_split(self, data, start, length, data_start, table, n_ref, text_base=0, file_len=None):
+        """SAMRecordReader over one FileSplit of SAM text; returns host numpy columns, as decode_split
+        (voffset = the plain file offset of each line)."""
+        rc, d = self.sam_decode_split_device(data, start, length, data_start, table, n_ref, text_base, file_len)
+        if rc:
+            return {"rc": rc, "error": self.last_error()}
+        h = Columns()
+        rc = self.L.hbam_columns_to_host(self.h, C.byref(d), C.byref(h))
+        if rc:
+            return {"rc": rc, "error": self.last_error()}
+        out = host_columns_to_numpy(h)
+        self.L.hbam_free_host_columns(C.byref(h))
+        out["rc"] = 0
         out["timing"] = self.timing()
         return out
 

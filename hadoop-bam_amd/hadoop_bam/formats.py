@@ -937,7 +937,9 @@ class BAMInputFormat:
 
 
 class AnySAMInputFormat(BAMInputFormat):
-    """AnySAMInputFormat.java:52-243 — BAM by extension or the 0x1f first byte."""
+    """AnySAMInputFormat.java:52-243 — the format by extension (.bam, .sam) or by the first byte
+    (0x1f, '@'); SAM paths go to SAMInputFormat / SAMRecordReader (sam.py), everything else to
+    BAMInputFormat."""
 
     TRUST_EXTS_PROPERTY = "hadoopbam.anysam.trust-exts"
 
@@ -946,6 +948,8 @@ class AnySAMInputFormat(BAMInputFormat):
         trust = str(conf.get(self.TRUST_EXTS_PROPERTY, "true")).lower() != "false"
         if trust and str(path).endswith(".bam"):
             return "BAM"
+        if trust and str(path).endswith(".sam"):
+            return "SAM"
         with open(path, "rb") as f:
             b = f.read(1)
         if b == b"\x1f":
@@ -953,3 +957,29 @@ class AnySAMInputFormat(BAMInputFormat):
         if b == b"@":
             return "SAM"
         return None
+
+    def _is_sam(self, path, conf):
+        """The format of a path is found once per (path, trust-exts) and kept, as the reference's
+        formatMap keeps it (:126-152)."""
+        if not isinstance(path, (str, os.PathLike)):
+            return False
+        conf = conf or Configuration()
+        key = (str(path), str(conf.get(self.TRUST_EXTS_PROPERTY, "true")).lower())
+        cache = self.__dict__.setdefault("_formats", {})
+        if key not in cache:
+            cache[key] = self.getFormat(path, conf)
+        return cache[key] == "SAM"
+
+    def createRecordReader(self, split, ctx=None):  # :163-189
+        # (ctx is a Configuration or nothing: BAMRecordReader.initialize reads anything else as an
+        # empty Configuration too)
+        conf = ctx if isinstance(ctx, Configuration) else None
+        if self._is_sam(split.getPath(), conf):
+            from .sam import SAMInputFormat
+            return SAMInputFormat().createRecordReader(split, conf)
+        return super().createRecordReader(split, ctx)
+
+    def getSplits(self, splits, cfg=None):  # :213-242: SAM splits stay as they are, ahead of the BAM ones
+        sam = [s for s in splits if self._is_sam(s.getPath(), cfg)]
+        bam = [s for s in splits if not self._is_sam(s.getPath(), cfg)]
+        return sam + (super().getSplits(bam, cfg) if bam else [])

@@ -22,7 +22,8 @@
  *   HBAM_ECLASSCAST   ClassCastException (an RG / PG attribute that is not a string)
  *
  * Library-specific codes (no reference counterpart): HBAM_ENOMEM, HBAM_EUNSUPPORTED
- * (BGZF block with ISIZE > 65536), HBAM_EDEVICE (HIP error), HBAM_EINVAL, HBAM_EMORE
+ * (BGZF block with ISIZE > 65536; SAM text the encoder does not restate), HBAM_EDEVICE (HIP
+ * error), HBAM_EINVAL, HBAM_EMORE
  * (the compressed window handed in ends before the split's last record).
  *
  * Inputs: an argument with `on_device` = 0 is host memory, copied in by the call; with
@@ -654,6 +655,81 @@ void hbam_vcf_release(hbam_ctx* ctx, hbam_vcf_columns* cols);
  * only), as hbam_gather_records.  Timing: pools_ms, pool_bytes. */
 int hbam_vcf_gather_lines(hbam_ctx* ctx, const hbam_vcf_columns* dv, const uint32_t* perm, uint64_t n,
                           uint8_t* out, uint64_t out_cap, uint64_t* out_off, uint64_t* total_bytes);
+
+/* ---- SAM text: SAMRecordReader (SAMRecordReader.java) over one FileSplit of SAMInputFormat ------
+ * The lines of the split become BAM records on the device (what SAMRecordWritable.write sends
+ * through the shuffle: BAMRecordCodec.encode whatever the record was read from), packed into the
+ * context's ubuf, and hbam_decode_split's own fixed-field and pool kernels run over them.  out is
+ * a device hbam_columns owned by the context exactly as after hbam_decode_split:
+ * rec_off[i + 1] == rec_off[i] + 4 + block_size[i], ubuf_len = the records' bytes, the usual slack
+ * behind them; hbam_columns_to_host, hbam_records_to_host, hbam_release_columns, hbam_sort_split,
+ * hbam_bai_build, hbam_summarize_ranges and hbam_fixmate take it unchanged.
+ * voffset[i] is NOT a BGZF virtual offset here: it is the plain file offset of line i's first byte.
+ *
+ * text = file bytes [text_base, text_base + text_len): one window of at most 2 GiB (HBAM_EINVAL
+ * above, before anything is read) that begins at or before the reader's first byte (data_start
+ * for start == 0, else start - 1), with the alignment contract of hbam_vcf_decode_split.  The
+ * host parses the header: data_start = the offset of the first byte after the last '@' line;
+ * table / names = the @SQ SN dictionary, name -> ordinal, in hbam_vcf_contig's layout.
+ *
+ * Lines (the rules of the VCF unit): a line ends at '\n'; a '\r' directly before it is dropped; a
+ * last line without '\n' is a line; there is no empty last line.
+ * The split [start, start + length) returns exactly the lines whose first byte b satisfies
+ * max(start, data_start) <= b < start + length (SAMRecordReader.initialize and WorkaroundingStream:
+ * a split at 0 begins at data_start, any other opens at start - 1 and discards through the first
+ * '\n', both read on through the first '\n' at or after start + length - 1).  Not restated:
+ *   - when the stream's remaining length reaches exactly 0 at the end of one of its reader's buffer
+ *     fills, the reference misses the '\n' at start + length - 1 and hands out one more line, which
+ *     the next split returns too (it depends on htsjdk's buffer size);
+ *   - a split with 0 < start < data_start (the reference feeds header lines to the record parser):
+ *     HBAM_EUNSUPPORTED is returned.
+ *   Divergence: start == 0 with length <= data_start returns no line (the reference returns the
+ *   first record).
+ * out->status = HBAM_EMORE as in hbam_vcf_decode_split: the window ends inside the last line the
+ * split would return, before file_len; call again with a longer window.
+ *
+ * Per line, a subset of htsjdk's SAMLineParser and BAMRecordCodec.encode (htsjdk is not in the
+ * reference tree: restated from memory, parity unpinned, DESIGN.md lists the rules).  At least 11
+ * tab-separated fields; FLAG, POS, MAPQ, PNEXT, TLEN as Integer.parseInt (FLAG and MAPQ are stored
+ * in 16 and 8 bits); RNAME / RNEXT through the dictionary ('*' and unknown names -1, RNEXT '='
+ * RNAME's index); pos = POS - 1; CIGAR '*' or (digits op)+ over MIDNSHP=X, lengths below 2^28; SEQ
+ * '*' or bytes of "=ACMGRSVTWYHKDBN" in either case, '.' read as N, packed high nibble first; QUAL
+ * '*' (l_seq bytes of 0xff) or SEQ's length of bytes - 33; bin = reg2bin(pos, end), end = pos + the
+ * CIGAR's reference length, pos + 1 when that is not positive or the read is unmapped (POS 0 gives
+ * 4680).  Tags XX:T:value: A; Z (bytes + NUL); i written with the narrowest type in htsjdk's order
+ * (I above int32, i above 65535, S above 32767, s above 255, C above 127, c down to -128, s down
+ * to -32768, i below); B:<cCsSiIf>,v,... (B, the subtype, an int32 count, the values); f and B:f
+ * correctly rounded to the nearest float32, ties to even, on this domain: [+-]? digits [. digits]
+ * ([eE][+-]? digits)?, at most 9 significant digits once leading and trailing zeros are dropped,
+ * and a decimal exponent in [-20, 20] once those digits are read as an integer (zero with any
+ * exponent); other float text is HBAM_EUNSUPPORTED.
+ * The first failing record ends the split: status, err_record = n_records = its index.
+ *   HBAM_EUNSUPPORTED  an H tag, a read name longer than 254 bytes, more than 65535 CIGAR ops, float
+ *                      text outside the domain;
+ *   HBAM_EFORMAT       (SAMFormatException) fewer than 11 fields, a non-numeric or out-of-range
+ *                      integer field, an empty field, a malformed CIGAR, a SEQ byte outside the
+ *                      table, a QUAL whose length differs from SEQ's, a QUAL with SEQ '*', a QUAL
+ *                      byte below 33, a malformed tag, an i value outside [-2^31, 2^32 - 1].
+ * A line is checked in field order, the tags left to right, the SEQ and QUAL bytes last.  The
+ * validations that depend on the stringency (SAMRecord.isValid, the POS / RNAME / CIGAR consistency
+ * warnings) are not restated.
+ *
+ * key: a placed record (flag bit 4 clear, ref >= 0, POS >= 0) gets hbam_decode_split's key; any
+ * other takes BAMRecordReader.getKey's second branch (:88-95; a SAM-text record has no variable
+ * binary representation): MurmurHash3 chained with an int seed over the read name (chars), the
+ * normalised read bases, the quality values and the CIGAR string (chars, "*" when empty), each
+ * step seeded with the previous result truncated to int; Integer.MAX_VALUE << 32 | hash.  The name
+ * and the CIGAR are hashed as the line writes them (a CIGAR length with leading zeros is not
+ * re-rendered: unpinned).
+ * Timing: scan_ms = structural pass, walk_ms = line scan, sizes and their scan, inflate_ms = the
+ * text-to-BAM encode (huffman_ms = its per-line pass, resolve_ms = its SEQ / QUAL pass), decode_ms /
+ * pools_ms as in hbam_decode_split, total_ms, comp_bytes = text_len, ubuf_bytes = the BAM bytes,
+ * n_records. */
+int hbam_sam_decode_split(hbam_ctx* ctx, const uint8_t* text, int on_device, uint64_t text_base,
+                          uint64_t text_len, uint64_t file_len, uint64_t start, uint64_t length,
+                          uint64_t data_start, const hbam_vcf_contig* table, uint32_t table_size,
+                          const uint8_t* names, uint64_t names_len, int32_t n_ref,
+                          hbam_columns* out);
 
 #ifdef __cplusplus
 }
