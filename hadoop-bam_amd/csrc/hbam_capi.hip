@@ -213,6 +213,20 @@ enum BufId {
   B_SAM_RSIZE,
   B_SAM_STATUS,
   B_SAM_DESC,
+  // SAM text output (hbam_samtext.hip)
+  B_ST_NAMES,
+  B_ST_NAMEOFF,
+  B_ST_UBUF,
+  B_ST_RECOFF,
+  B_ST_LEN,
+  B_ST_STATUS,
+  B_ST_DFLAG,
+  B_ST_DESC,
+  B_ST_LINEOFF,
+  B_ST_DPOS,
+  B_ST_DEFERRED,
+  B_ST_SMALL,
+  B_ST_TEXT,
   B_COUNT_ALL
 };
 
@@ -2679,3 +2693,4 @@ extern "C" int64_t hbam_bgzf_compress(hbam_ctx* c, const uint8_t* src, int src_o
 #include "hbam_bai.hip"
 #include "hbam_vcf.hip"
 #include "hbam_sam.hip"
+#include "hbam_samtext.hip"

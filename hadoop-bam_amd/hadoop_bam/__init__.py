@@ -3,7 +3,8 @@
 Mirrors org.seqdoop.hadoop_bam.{BAMInputFormat, BAMRecordReader, FileVirtualSplit,
 SAMRecordWritable, BAMSplitGuesser, util.BGZFSplitGuesser, util.BGZFBlockIndexer/BGZFBlockIndex/BGZFSplitFileInputFormat, SplittingBAMIndex, SplittingBAMIndexer}, the Sort plugin's
 shuffle sort (cli/plugins/Sort) and its BAM output (BAMRecordWriter, KeyIgnoringBAMOutputFormat,
-util.SAMOutputPreparer, cli.Utils.mergeSAMInto); compute runs
+util.SAMOutputPreparer, cli.Utils.mergeSAMInto) and its SAM text output (SAMRecordWriter,
+KeyIgnoringAnySAMOutputFormat, the View plugin); compute runs
 in libhbam.so (HIP, gfx950) through the C ABI of include/hbam.h.
 """
 from ._lib import Context, HbamUnavailable, load  # noqa: F401
@@ -18,3 +19,6 @@ from .output import (  # noqa: F401
 from .index import BAMIndex, BAMIndexer, IndexedBAMReader, parse_region  # noqa: F401
 from .sam import (  # noqa: F401
     SAMFormat, SAMInputFormat, SAMRecordReader, SAMUnsupportedException, read_sam_text_header)
+from .sam_text import (  # noqa: F401
+    AnySAMOutputFormat, KeyIgnoringAnySAMOutputFormat, KeyIgnoringSAMRecordWriter, SAMRecordWriter,
+    java_float_to_string, render_record, view)

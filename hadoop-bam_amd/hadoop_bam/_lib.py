@@ -63,7 +63,7 @@ EXPORTS = [
     "hbam_split_read_bytes", "hbam_rewrite_groups", "hbam_records_to_host", "hbam_split_records_to_host",
     "hbam_bai_bound", "hbam_bai_build", "hbam_overlap_filter",
     "hbam_vcf_decode_split", "hbam_vcf_columns_to_host", "hbam_vcf_release", "hbam_vcf_gather_lines",
-    "hbam_sam_decode_split",
+    "hbam_sam_decode_split", "hbam_sam_render",
 ]
 
 # hbam_read_fn: int64_t read(void* user, uint64_t offset, uint64_t len, uint8_t* dst)
@@ -165,6 +165,14 @@ class VcfColumnsC(C.Structure):
         ("line_len", C.c_void_p), ("tab", C.c_void_p), ("chrom", C.c_void_p), ("pos", C.c_void_p),
         ("ref_len", C.c_void_p), ("key", C.c_void_p), ("text", C.c_void_p), ("text_base", C.c_uint64),
         ("text_len", C.c_uint64),
+    ]
+
+
+class SamTextC(C.Structure):
+    _fields_ = [
+        ("n_records", C.c_uint64), ("status", C.c_int32), ("pad", C.c_int32), ("err_record", C.c_uint64),
+        ("text_len", C.c_uint64), ("text", C.c_void_p), ("line_off", C.c_void_p), ("n_deferred", C.c_uint64),
+        ("deferred", C.c_void_p),
     ]
 
 
@@ -287,6 +295,7 @@ def load(path=None):
         "hbam_sam_decode_split": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
                                             C.c_uint64, C.c_uint64, vp, C.c_uint32, vp, C.c_uint64, C.c_int32,
                                             C.POINTER(Columns)]),
+        "hbam_sam_render": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_int, vp, vp, C.c_int32, C.POINTER(SamTextC)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name, None)
@@ -1025,6 +1034,50 @@ class Context:
         out["rc"] = 0
         out["timing"] = self.timing()
         return out
+
+    # ---- SAM text output (hbam_samtext.hip) --------------------------------------------------------
+    def sam_render_device(self, ubuf, rec_off, n, names, perm=None, on_device=True):
+        """hbam_sam_render -> (rc, device SamTextC).  on_device: ubuf / rec_off / perm are device
+        pointers (ints or ctypes pointers: a decode's columns, a sorted run, hbam_overlap_filter's
+        list); else ubuf is host bytes and rec_off a host uint64 array of n + 1 offsets.  names = the
+        dictionary names (bytes) in order."""
+        names = [bytes(x) for x in names]
+        noff = np.zeros(len(names) + 1, np.uint32)
+        noff[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64)
+        nm = np.frombuffer(b"".join(names) or b"\0", np.uint8)
+        t = SamTextC()
+        vp = C.c_void_p
+        if on_device:
+            args = [C.cast(x, vp) if not isinstance(x, (int, type(None))) else vp(x) for x in (ubuf, rec_off, perm)]
+            keep = None
+        else:
+            if perm is not None:
+                raise ValueError("perm needs device arguments")
+            ro = np.ascontiguousarray(rec_off, np.uint64)
+            if len(ro) != n + 1:
+                raise ValueError("rec_off must hold n + 1 offsets")
+            ub = np.frombuffer(bytes(ubuf), np.uint8) if not isinstance(ubuf, np.ndarray) else np.ascontiguousarray(ubuf)
+            if n and int(ro[n]) > ub.size:
+                raise ValueError("rec_off runs past the record bytes")
+            keep = (ro, ub)
+            args = [vp(ub.ctypes.data if ub.size else 0), vp(ro.ctypes.data), vp(None)]
+        rc = self.L.hbam_sam_render(self.h, args[0], args[1], args[2], int(n), int(bool(on_device)),
+                                    vp(nm.ctypes.data), vp(noff.ctypes.data), len(names), C.byref(t))
+        del keep
+        return rc, t
+
+    def sam_render(self, ubuf, rec_off, n, names, perm=None, on_device=True):
+        """hbam_sam_render and a host copy of what it wrote -> dict: n, status, err_record, text
+        (bytes; a deferred line is empty), line_off (uint64[n + 1]), deferred (uint32, ascending
+        output positions), timing."""
+        rc, t = self.sam_render_device(ubuf, rec_off, n, names, perm, on_device)
+        if rc:
+            return {"rc": rc, "error": self.last_error()}
+        k = int(t.n_records)
+        return {"rc": 0, "n": k, "status": int(t.status), "err_record": int(t.err_record),
+                "text": self._d2h(t.text, int(t.text_len), np.uint8).tobytes(),
+                "line_off": self._d2h(t.line_off, k + 1, np.uint64),
+                "deferred": self._d2h(t.deferred, int(t.n_deferred), np.uint32), "timing": self.timing()}
 
     def vcf_gather_lines(self, dcols, perm=None, n=None):
         """hbam_vcf_gather_lines over the device columns of a keep_text decode: lines perm[0..n)

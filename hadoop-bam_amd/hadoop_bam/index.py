@@ -321,24 +321,33 @@ class IndexedBAMReader:
             for _ in range(4):  # a read of up to ~250 kB of blocks more per round
                 ce = block_end(ce)
 
-    def _query(self, ref, beg, end, contained):
+    def query_columns(self, ref, beg=0, end=0, contained=False):
+        """The query on the device, chunk by chunk: yields (d, k, idx) per index chunk, d the device
+        columns of the chunk's decode and idx a device u32 list of the k records of d that overlap
+        (or are contained in) the region, ascending (hbam_overlap_filter): what hbam_gather_records
+        and hbam_sam_render take as perm.  All three are valid until the next chunk is asked for.  A
+        chunk whose decode ended in a status raises it once the chunk has been handed out."""
         r = self._reference(ref)
         chunks = self.index.span_overlapping(r, beg, end)
         self.last_query = {"chunks": chunks, "comp_bytes": 0, "decoded_records": 0, "widened": 0}
-        out = []
         for vbeg, vend in chunks:
             d = self._decode_chunk(vbeg, vend)
             self.last_query["decoded_records"] += int(d.n_records)
             k, idx = self.ctx.overlap_filter(d, r, beg, end, contained)
             try:
-                voff, payload, off = self.ctx.gather_to_host(d, idx, k)
+                yield d, k, idx
             finally:
                 self.ctx.L.hbam_device_free(self.ctx.h, idx)
+            st = int(d.status)  # never HBAM_EMORE here: _decode_chunk widens or raises
+            if st != _lib.HBAM_OK:
+                _raise(st, "at record %d of chunk %#x-%#x" % (int(d.n_records), vbeg, vend))
+
+    def _query(self, ref, beg, end, contained):
+        out = []
+        for d, k, idx in self.query_columns(ref, beg, end, contained):
+            voff, payload, off = self.ctx.gather_to_host(d, idx, k)
             for j in range(k):
                 rec = BAMRecordBytes(payload[int(off[j]):int(off[j + 1])].tobytes())
                 rec.voffset = int(voff[j])
                 out.append(rec)
-            st = int(d.status)  # never HBAM_EMORE here: _decode_chunk widens or raises
-            if st != _lib.HBAM_OK:
-                _raise(st, "at record %d of chunk %#x-%#x" % (int(d.n_records), vbeg, vend))
         return out

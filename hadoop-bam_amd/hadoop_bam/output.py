@@ -2,7 +2,8 @@
 mirrors BAMRecordWriter (BAMRecordWriter.java:48-141), KeyIgnoringBAMRecordWriter,
 KeyIgnoringBAMOutputFormat (KeyIgnoringBAMOutputFormat.java:43-98),
 util.SAMOutputPreparer.prepareForRecords (:58-95) and cli.Utils.mergeSAMInto (:333-356)
-— the pieces the Sort plugin uses to write its sorted BAM.
+— the pieces the Sort plugin uses to write its sorted BAM.  The SAM halves of the preparer and
+the merge write header text; the SAM record writers are in sam_text.py.
 
 The compressed bytes are the device compressor's, not zlib's: what the reference's tests
 check, and what these classes guarantee, is the inflated stream (header bytes, then every
@@ -201,12 +202,18 @@ class KeyIgnoringBAMOutputFormat:
 
 
 class SAMOutputPreparer:
-    """util/SAMOutputPreparer.java:58-95 for BAM: the header (magic, text, dictionary) through
-    a BGZF stream, flushed; returns the stream for the records."""
+    """util/SAMOutputPreparer.java:58-95.  BAM: the header (magic, text, dictionary) through a
+    BGZF stream, flushed; returns the stream for the records.  SAM: the header text written to
+    `out`, which is returned."""
 
     def prepareForRecords(self, out, fmt, header, ctx=None):
+        if fmt == "SAM":
+            from .sam_text import header_text
+            out.write(header_text(header))
+            out.flush()
+            return out
         if fmt != "BAM":
-            raise ValueError("only BAM output is on this path")
+            raise ValueError("unknown SAM format: %r" % (fmt,))
         sink = _BGZFSink(out, ctx or _lib.Context(0))
         sink.write(header.to_bam_bytes())
         sink.flush()
@@ -220,8 +227,9 @@ def get_mergeable_work_file(directory, base_prefix, base_postfix, work_filename,
 
 
 def merge_sam_into(out_path, directory, base_prefix, base_postfix, header, work_filename="",
-                   ctx=None):
-    """cli/Utils.mergeSAMInto (:333-356) for BAM: the merged header through its own BGZF
+                   ctx=None, fmt="BAM"):
+    """cli/Utils.mergeSAMInto (:333-356).  fmt "SAM": the merged header's text, the work files
+    concatenated, no terminator (:355).  fmt "BAM" (the default): the merged header through its own BGZF
     stream (SAMOutputPreparer), the work files (mergeInto :194-229: glob
     prefix+work+postfix-[0-9]{6}*, in name order) copied byte for byte and deleted, then the
     BGZF EOF block.  `header` is getSAMHeaderMerger(conf).getMergedHeader() (:348-349): a
@@ -233,7 +241,7 @@ def merge_sam_into(out_path, directory, base_prefix, base_postfix, header, work_
     pat = base_prefix + work_filename + base_postfix + "-" + "[0-9]" * 6 + "*"
     parts = sorted(f for f in os.listdir(directory) if fnmatch.fnmatchcase(f, pat))
     with open(out_path, "wb") as outs:
-        SAMOutputPreparer().prepareForRecords(outs, "BAM", header, ctx)
+        SAMOutputPreparer().prepareForRecords(outs, fmt, header, ctx)
         for f in parts:
             with open(os.path.join(directory, f), "rb") as fin:
                 while True:
@@ -241,6 +249,7 @@ def merge_sam_into(out_path, directory, base_prefix, base_postfix, header, work_
                     if not b:
                         break
                     outs.write(b)
-        outs.write(EMPTY_GZIP_BLOCK)
+        if fmt == "BAM":
+            outs.write(EMPTY_GZIP_BLOCK)
     for f in parts:
         os.remove(os.path.join(directory, f))

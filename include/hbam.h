@@ -731,6 +731,62 @@ int hbam_sam_decode_split(hbam_ctx* ctx, const uint8_t* text, int on_device, uin
                           const uint8_t* names, uint64_t names_len, int32_t n_ref,
                           hbam_columns* out);
 
+/* ---- SAM text output: SAMTextWriter.writeAlignment over packed BAM records ----------------------
+ * The inverse of hbam_sam_decode_split: SAMRecordWriter, the SAM half of AnySAMOutputFormat and the
+ * View plugin's printing.  ubuf / rec_off = packed BAM records (block_size + record each) and their
+ * offsets, u64[count + 1] with rec_off[i + 1] - rec_off[i] >= 4 + block_size of record i, and 64
+ * readable bytes behind the last record: hbam_columns.ubuf / rec_off of any decode, a
+ * hbam_sorted_run's payload / offsets.  Output line k is record perm[k] (device u32[n], each an index
+ * into rec_off, e.g. hbam_overlap_filter's list); perm == NULL means the identity, as in
+ * hbam_gather_records.  on_device == 0: ubuf and rec_off are host pointers, the library uploads them
+ * with the slack, and perm must be NULL.  names / name_off are host arrays whatever on_device says:
+ * the dictionary names back to back and their n_ref + 1 offsets.  n == 0 is legal and gives empty
+ * text.  out's arrays are device arrays owned by the context until its next call.
+ *
+ * Per record, htsjdk's SAMTextWriter.writeAlignment (htsjdk is not in the reference tree: restated
+ * from memory, parity unpinned, DESIGN.md lists the rules): QNAME the l_read_name - 1 name bytes; FLAG
+ * decimal; RNAME the dictionary name, '*' for -1; POS (int32)(pos + 1); MAPQ; CIGAR len op over
+ * MIDNSHP=X, '*' for no ops; RNEXT '=' when next_ref_id >= 0 and equal to ref_id, else the name or
+ * '*'; PNEXT next_pos + 1; TLEN; SEQ through "=ACMGRSVTWYHKDBN", '*' when l_seq == 0; QUAL '*' when
+ * l_seq == 0 or the first quality byte is 0xff, else each byte + 33; the tags in record order as
+ * \tXX:T:value: A the raw byte, Z the bytes up to the NUL (empty: "XX:Z:"), every integer width as i
+ * in decimal (C, S, I unsigned), arrays B:<sub>,v,v... (no elements: "XX:B:c"); every line ends '\n'.
+ * Floats: htsjdk writes Float.toString.  The device renders a float32 (f and B:f) only where that
+ * text is trivially exact: an integer value with |v| < 10^7 as "N.0", and 0.0 / -0.0.  A record
+ * with any other float, or an H tag, is DEFERRED to the caller: its line is empty in text
+ * (line_off[k + 1] == line_off[k]) and its output position is listed in deferred; the caller renders
+ * that line and splices it in at line_off[k].  A deferred record is validated like any other.
+ *
+ * The first failing record ends the output: status, err_record = n_records = its output position;
+ * text_len, line_off and deferred cover the lines before it.
+ *   HBAM_EFORMAT  block_size < 32 + l_read_name + 4 n_cigar + (l_seq + 1) / 2 + l_seq, or 4 +
+ *                 block_size beyond the record's rec_off slot; l_read_name == 0; l_seq < 0; a tag
+ *                 that runs past the record; an unknown tag type or B subtype; a negative B count;
+ *                 a Z or H without its NUL;
+ *   HBAM_EREFID   (IllegalArgumentException) ref_id or next_ref_id outside [-1, n_ref); a CIGAR op
+ *                 code above 8 (as hbam_summarize_ranges reports it); a quality byte above 93 when
+ *                 the 0xff rule does not apply;
+ *   HBAM_EUNSUPPORTED  a line of more than 2^31 - 1 bytes.
+ * A record is checked in that order, the tags left to right, the quality bytes last.  Every length
+ * taken from a record is checked against block_size before it is used: a malformed record gives a
+ * status, never a read outside the record and the slack or a write outside text.
+ * Timing: total_ms, walk_ms = sizes + scans, huffman_ms = the per-line pass (fields 1-9, tags),
+ * resolve_ms = the SEQ / QUAL pass, n_records, ubuf_bytes = the text bytes. */
+typedef struct hbam_sam_text {
+  uint64_t n_records;
+  int32_t status;
+  int32_t pad;
+  uint64_t err_record;
+  uint64_t text_len;
+  uint8_t* text;       /* device, owned by the context until the next call */
+  uint64_t* line_off;  /* device u64[n+1]; line i = text[line_off[i], line_off[i+1]) with its '\n'; empty = deferred */
+  uint64_t n_deferred;
+  uint32_t* deferred;  /* device u32[n_deferred], ascending output positions */
+} hbam_sam_text;
+int hbam_sam_render(hbam_ctx* ctx, const uint8_t* ubuf, const uint64_t* rec_off, const uint32_t* perm,
+                    uint64_t n, int on_device, const uint8_t* names, const uint32_t* name_off,
+                    int32_t n_ref, hbam_sam_text* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,11 @@ public final class Hbam implements AutoCloseable {
   static final MethodHandle BAI_BUILD = fn("hbam_bai_build", FunctionDescriptor.of(J, A, A, I, J, A, J, A));
   static final MethodHandle OVERLAP_FILTER = fn("hbam_overlap_filter",
       FunctionDescriptor.of(J, A, A, I, J, J, I, A));
+  // SAM text output (SAMRecordWriter, AnySAMOutputFormat's SAM half, View): records on the device ->
+  // SAMTextWriter lines; out is an hbam_sam_text (n_records, status, pad, err_record, text_len, text,
+  // line_off, n_deferred, deferred: 64 bytes)
+  static final MethodHandle SAM_RENDER = fn("hbam_sam_render",
+      FunctionDescriptor.of(I, A, A, A, A, J, I, A, A, I, A));
 
   /** hbam_bcf_header: n_contig, n_sample, n_dict, bgzf, header_len, first_voffset (32 bytes). */
   public static final StructLayout BCF_HEADER = MemoryLayout.structLayout(
