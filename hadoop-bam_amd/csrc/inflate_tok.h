@@ -10,7 +10,7 @@
 // `s_waitcnt vmcnt(...)` on the critical path of EVERY loop iteration, because some lane of
 // the 64 is always refilling and the wait is per wave.  Here the input moves in wave-uniform
 // epochs instead:
-//   * each lane holds 32 compressed bytes in two register banks plus a 64-bit bit buffer;
+//   * each lane holds 32 compressed bytes in two register banks and a bit cursor over them;
 //   * every TOK_K iterations (the same iteration for every active lane) a lane merges
 //     the 16-byte quad it requested at the previous epoch into a free bank and requests the
 //     next one, so a load has a whole epoch to land before anything waits on it;
@@ -51,6 +51,10 @@ namespace hbam {
 #ifndef TOK_ITER
 #define TOK_ITER(v) (void)0
 #endif
+// ... and of those the ones a running lane skips because its banks are short of bits (stalls)
+#ifndef TOK_STALL
+#define TOK_STALL(c, v) (void)0
+#endif
 
 constexpr uint32_t TOK_K = 4;  // symbol-loop iterations per input epoch (power of two)
 
@@ -71,28 +75,45 @@ constexpr uint32_t TOK_LENS_END = 352;  // = LENS_SLOT (hbam_internal.h)
 // ---- input: two register banks + one quad in flight ------------------------------------
 typedef const __attribute__((address_space(1))) u32x4_t* gq_ptr;  // global (not flat) loads
 __device__ __forceinline__ u32x4_t ein_load(const uint4* p) { return *(gq_ptr)p; }
+// The reader is a bit cursor over the ring of the two banks: an iteration forms the 64 bits at
+// the cursor once (ein_window: three ring dwords through shared select levels, two
+// v_alignbit_b32), reads every code and extra field at an offset into that window and adds the
+// offsets' sum to the cursor.  cur, fill and total count stream bits from the start of the first
+// quad (bit 0 = bit 0 of the quad that holds the stream's first byte), so cur & 255 is the ring
+// position and cur & 7 the phase inside the stream's byte.
 struct EIn {
   const uint4* fp;    // quad held in t (merged at the next epoch); == fend when the fetch is done
   const uint4* fend;  // one past the last quad that holds stream bytes
   const uint4* safe;  // an address already read (target of the dummy load after the fetch)
   uint4 q0, q1;       // banks: stream dwords, ring positions 0..3 and 4..7
   u32x4_t t;          // quad requested at the last epoch
-  uint32_t rd;        // next ring position to move into bb
-  uint32_t nv;        // unread dwords in the banks (from rd)
-  uint64_t bb;        // bit buffer, LSB first
-  uint32_t bc;        // valid bits in bb
-  uint32_t consumed;  // stream bits consumed
-  uint32_t total;     // 8 * deflated bytes
+  uint32_t cur;       // bit cursor: the next stream bit to read
+  uint32_t fill;      // fill mark: the banks hold the bits [fill - 256, fill); 128 per merged quad
+  uint32_t total;     // the cursor at the end of the stream: 8 * (address & 15) + 8 * deflated bytes
 };
 
+// the two dwords of a 64-bit funnel: ((hi:lo) >> (s & 31)) & 0xffffffff, v_alignbit_b32 (a shift
+// of 0 gives lo, so no guard)
+__device__ __forceinline__ uint32_t ein_align(uint32_t hi, uint32_t lo, uint32_t s) {
+  return (uint32_t)((((uint64_t)hi << 32) | lo) >> (s & 31u));
+}
+// The 64 stream bits at the cursor: ring dwords idx, idx + 1, idx + 2 (idx = (cur >> 5) & 7).
 // (component-wise selects: a select between two uint4 lvalues becomes a select between their
-// addresses, which pins the whole reader in scratch)
-__device__ __forceinline__ uint32_t ein_sel(const EIn& e, uint32_t i) {
-  const bool h = (i & 4u) != 0u, z = (i & 2u) != 0u;
-  const uint32_t x = h ? e.q1.x : e.q0.x, y = h ? e.q1.y : e.q0.y;
-  const uint32_t zz = h ? e.q1.z : e.q0.z, w = h ? e.q1.w : e.q0.w;
-  const uint32_t a = z ? zz : x, b = z ? w : y;
-  return (i & 1u) ? b : a;
+// addresses, which pins the whole reader in scratch.)  The first level picks by idx & 1 inside
+// each pair of neighbours and serves all three dwords: a[k] is dword 2k or 2k + 1, b[k] the one
+// after it; the other two levels pick the pair.
+__device__ __forceinline__ uint64_t ein_window(const EIn& e) {
+  const uint32_t idx = e.cur >> 5;
+  const bool o = (idx & 1u) != 0u, z = (idx & 2u) != 0u, h = (idx & 4u) != 0u;
+  const uint32_t a0 = o ? e.q0.y : e.q0.x, a1 = o ? e.q0.w : e.q0.z;
+  const uint32_t a2 = o ? e.q1.y : e.q1.x, a3 = o ? e.q1.w : e.q1.z;
+  const uint32_t b0 = o ? e.q0.z : e.q0.y, b1 = o ? e.q1.x : e.q0.w;
+  const uint32_t b2 = o ? e.q1.z : e.q1.y, b3 = o ? e.q0.x : e.q1.w;
+  const uint32_t d0 = h ? (z ? a3 : a2) : (z ? a1 : a0);
+  const uint32_t d1 = h ? (z ? b3 : b2) : (z ? b1 : b0);
+  const uint32_t d2 = h ? (z ? a0 : a3) : (z ? a2 : a1);
+  const uint32_t lo = ein_align(d1, d0, e.cur), hi = ein_align(d2, d1, e.cur);
+  return (uint64_t)hi << 32 | lo;
 }
 __device__ __forceinline__ void ein_init(EIn& e, const uint8_t* p, uint32_t nbytes) {
   const uintptr_t a = (uintptr_t)p & 15u;
@@ -104,35 +125,9 @@ __device__ __forceinline__ void ein_init(EIn& e, const uint8_t* p, uint32_t nbyt
   e.fp = base + 2;
   if (e.fp > e.fend) e.fp = e.fend;
   e.t = ein_load(e.fp < e.fend ? e.fp : e.safe);
-  const uint32_t r = (uint32_t)(a >> 2);
-  const uint32_t sh = 8u * (uint32_t)(a & 3u);
-  e.bb = (uint64_t)(ein_sel(e, r) >> sh);
-  e.bc = 32u - sh;
-  e.rd = r + 1u;
-  e.nv = 8u - e.rd;
-  e.consumed = 0;
-  e.total = nbytes * 8u;
-}
-// one dword from the banks into bb (the stall check guarantees the banks hold what is needed)
-__device__ __forceinline__ void ein_refill(EIn& e) {
-  if (e.bc <= 32u && e.nv != 0u) {
-    e.bb |= (uint64_t)ein_sel(e, e.rd) << e.bc;
-    e.bc += 32u;
-    e.rd = (e.rd + 1u) & 7u;
-    --e.nv;
-  }
-}
-// the same without a branch (the fast path: a branch around it costs every iteration the exec-mask
-// bookkeeping, since some lane of 64 nearly always needs the dword).  With the branchless length /
-// distance bases below: Huffman 33.9 -> 32.1 ms at 5 GB, same output
-// (profiles/r05/ab/huffman_branchless_refill_bases_5g.txt)
-__device__ __forceinline__ void ein_refill_sel(EIn& e) {
-  const bool need = e.bc <= 32u && e.nv != 0u;
-  const uint64_t add = (uint64_t)ein_sel(e, e.rd) << (e.bc & 63u);
-  e.bb |= need ? add : 0ull;
-  e.bc += need ? 32u : 0u;
-  e.rd = need ? ((e.rd + 1u) & 7u) : e.rd;
-  e.nv -= need ? 1u : 0u;
+  e.cur = 8u * (uint32_t)a;
+  e.fill = 256u;
+  e.total = e.cur + nbytes * 8u;
 }
 // length / distance bases without branches (DEFLATE tables as arithmetic; RFC 1951 3.2.5)
 // (one formula for every code, the exceptions as constant selects: written as a select between
@@ -149,10 +144,11 @@ __device__ __forceinline__ void dist_base_sel(uint32_t d, uint32_t& base, uint32
   extra = ex;
   base = ((2u + (d & 1u)) << ex) + 1u - (d < 2u ? 2u : 0u);
 }
-// epoch boundary: merge the quad in flight into the free bank, request the next one
+// epoch boundary: merge the quad in flight into the bank that lies wholly behind the cursor,
+// request the next one.  fill grows by 128 per quad, so the bank it overwrites is (fill >> 7) & 1.
 __device__ __forceinline__ void ein_epoch_merge(EIn& e) {
-  if (e.fp < e.fend && e.nv <= 4u) {
-    const bool hi = (((e.rd + e.nv) & 7u) >> 2) != 0u;
+  if (e.fp < e.fend && e.fill - e.cur <= 128u) {
+    const bool hi = (e.fill & 128u) != 0u;
     const u32x4_t t = e.t;
     e.q0.x = hi ? e.q0.x : t[0];
     e.q0.y = hi ? e.q0.y : t[1];
@@ -162,7 +158,7 @@ __device__ __forceinline__ void ein_epoch_merge(EIn& e) {
     e.q1.y = hi ? t[1] : e.q1.y;
     e.q1.z = hi ? t[2] : e.q1.z;
     e.q1.w = hi ? t[3] : e.q1.w;
-    e.nv += 4u;
+    e.fill += 128u;
     ++e.fp;
   }
 }
@@ -173,25 +169,24 @@ __device__ __forceinline__ void ein_epoch(EIn& e) {
 }
 // bits the lane can use without another epoch
 __device__ __forceinline__ bool ein_short(const EIn& e, uint32_t need) {
-  return e.bc + 32u * e.nv < need && e.fp < e.fend;
+  return e.fill - e.cur < need && e.fp < e.fend;
 }
-// synchronous top-up (header phase): epochs until `need` bits are buffered or the fetch is done
+// synchronous top-up (header phase): epochs until `need` bits are in the banks or the fetch is done
 __device__ __forceinline__ void ein_ensure(EIn& e, uint32_t need) {
   while (ein_short(e, need)) ein_epoch(e);
-  ein_refill(e);
-  ein_refill(e);
 }
-__device__ __forceinline__ uint32_t ein_avail(const EIn& e) { return e.total - e.consumed; }
-__device__ __forceinline__ uint32_t ein_peek(const EIn& e, uint32_t n) {
-  return (uint32_t)e.bb & ((1u << n) - 1u);
+__device__ __forceinline__ uint32_t ein_avail(const EIn& e) { return e.total - e.cur; }
+__device__ __forceinline__ uint32_t ein_peek(uint64_t w, uint32_t n) {
+  return (uint32_t)w & ((1u << n) - 1u);
 }
-__device__ __forceinline__ void ein_drop(EIn& e, uint32_t n) {
-  e.bb >>= n;
-  e.bc -= n;
-  e.consumed += n;
+__device__ __forceinline__ void ein_drop(EIn& e, uint32_t n) { e.cur += n; }
+// drop n bits of a window held in w as well (the careful symbol and the header phase)
+__device__ __forceinline__ void ein_take(EIn& e, uint64_t& w, uint32_t n) {
+  w >>= n;
+  e.cur += n;
 }
-__device__ __forceinline__ uint32_t ein_rev15(const EIn& e) {
-  return __builtin_bitreverse32((uint32_t)e.bb) >> 17;
+__device__ __forceinline__ uint32_t ein_rev15(uint64_t w) {
+  return __builtin_bitreverse32((uint32_t)w) >> 17;
 }
 
 // ---- packed canonical decode tables (symbol loop) ---------------------------------------
@@ -511,6 +506,7 @@ __device__ __forceinline__ uint32_t quad_byte(const uint4& q, uint32_t j) {  // 
 //   TOK_FIT_M11   ... and none longer than 11 (lim[10 ..] == 32768).
 // The incomplete-but-legal sets (a single distance code, no distance code) get none of them.
 constexpr uint32_t TOK_BUILT = 1u, TOK_FIT_FULL = 2u, TOK_FIT_LOW = 4u, TOK_FIT_M11 = 8u;
+constexpr uint32_t TOK_FIT_MAXL = 8u;  // ... and from this bit on the longest code length of the set (0..15)
 // Out of line: called once per DEFLATE block, and inlining its unrolled counters into the
 // kernel pushes the symbol loop's state into scratch.
 __device__ __attribute__((noinline)) uint32_t tok_build(const uint8_t* __restrict__ lens, int n,
@@ -596,13 +592,15 @@ __device__ __attribute__((noinline)) uint32_t tok_build(const uint8_t* __restric
       }
     }
   }
-  return fit;
+  return fit | maxl << TOK_FIT_MAXL;
 }
 
 // One iteration of the symbol loop with >= 64 stream bits left: two lit/len codes + length
 // extra + distance code + distance extra (15+15+5+15+13) fit, so zlib's end-of-input outcomes
-// cannot occur and after one refill (>= 33 bits in bb) none is checked.  A literal is followed
-// by a second lit/len decode in the same iteration (the wave pays for the match path once per
+// cannot occur and none is checked.  The caller has seen to it that the banks hold what the
+// block's tables can make an iteration read (tok_epoch's `need`); the one window's bits past that
+// may be stale, and only fields that turn out unused (the second lookup after a length symbol,
+// the distance lookup after a literal) ever look at them.  A literal is followed by a second lit/len decode in the same iteration (the wave pays for the match path once per
 // iteration either way, and most symbols are literals).  Every lane runs the whole iteration
 // and flags say which of its results count (SIMT runs the union of the paths anyway); the
 // first exit code a lane meets wins, as zlib's early returns.  Both lit/len lookups run before
@@ -645,24 +643,23 @@ __device__ __forceinline__ uint32_t tok_fast_spec(EIn& in, const HuffP& hl, cons
                                                   const uint8_t* __restrict__ syms_ll,
                                                   const uint8_t* __restrict__ syms_d, TSink& sink,
                                                   uint32_t& op, uint32_t isize, TPend& pd) {
-  ein_refill_sel(in);
+  const uint64_t w = ein_window(in);  // the iteration's <= 63 bits, read at the running offset `off`
   uint32_t L1, idx1, hi1 = 0, L2, idx2, hi2 = 0;
-  const bool ok1 = huffp_lookup<true, SPEC ? 1 : 0, 7>(hl, ein_rev15(in), L1, idx1, hi1);
+  const bool ok1 = huffp_lookup<true, SPEC ? 1 : 0, 7>(hl, ein_rev15(w), L1, idx1, hi1);
   const uint32_t l1 = ok1 ? L1 : 0u;
-  const uint32_t v2 = __builtin_bitreverse32((uint32_t)(in.bb >> l1)) >> 17;
-  const bool ok2 = huffp_lookup<true, SPEC ? 1 : 0, 7>(hl, v2, L2, idx2, hi2);
+  const bool ok2 = huffp_lookup<true, SPEC ? 1 : 0, 7>(hl, ein_rev15(w >> l1), L2, idx2, hi2);
   const uint32_t sym1 = (uint32_t)syms_ll[ok1 ? idx1 : 0u] | hi1;
   const uint32_t sym2 = (uint32_t)syms_ll[ok2 ? idx2 : 0u] | hi2;
   sink.put(pd.op1, pd.P, pd.nb);  // the previous iteration's packet
   uint32_t ex = ok1 ? 0u : 3u;
-  ein_drop(in, l1);
+  uint32_t off = l1;
   const bool lit1 = ok1 && hi1 == 0u;
   if (!INTERIOR) ex = (ex == 0u && lit1 && op == isize) ? 2u : ex;
   const bool emit1 = ex == 0u && lit1;
   const uint32_t op1 = op;
   op += emit1 ? 1u : 0u;
   ex = (emit1 && !ok2) ? 3u : ex;
-  ein_drop(in, (emit1 && ok2) ? L2 : 0u);
+  off += (emit1 && ok2) ? L2 : 0u;
   const bool lit2 = emit1 && ok2 && hi2 == 0u;
   if (!INTERIOR) ex = (ex == 0u && lit2 && op == isize) ? 2u : ex;
   const bool emit2 = ex == 0u && lit2;
@@ -674,23 +671,22 @@ __device__ __forceinline__ uint32_t tok_fast_spec(EIn& in, const HuffP& hl, cons
   const bool dom = ism && m > 256u && m <= 285u;
   uint32_t lbase, lext;
   length_base_sel(dom ? m : 257u, lbase, lext);
-  ein_refill_sel(in);
   lext = dom ? lext : 0u;
-  const uint32_t mlen = lbase + ein_peek(in, lext);
-  ein_drop(in, lext);
+  const uint32_t mlen = lbase + ein_peek(w >> off, lext);
+  off += lext;
   uint32_t L, idx, dh;
-  const bool okd = huffp_lookup<false, SPEC ? 1 : 0, SPEC ? 5 : 7>(hd, ein_rev15(in), L, idx, dh);
+  const bool okd = huffp_lookup<false, SPEC ? 1 : 0, SPEC ? 5 : 7>(hd, ein_rev15(w >> off), L, idx, dh);
   const uint32_t dsym = syms_d[okd ? idx : 0u];
   sink.mark_if(pd.em, pd.opm);  // the previous iteration's match mark
   ex = (dom && !okd) ? 3u : ex;
-  ein_drop(in, (dom && okd) ? L : 0u);
+  off += (dom && okd) ? L : 0u;
   ex = (dom && okd && dsym > 29u) ? 3u : ex;
   const bool dom2 = dom && ex == 0u;
   uint32_t dbase, dext;
   dist_base_sel(dom2 ? dsym : 0u, dbase, dext);
   dext = dom2 ? dext : 0u;
-  const uint32_t dist = dbase + ein_peek(in, dext);
-  ein_drop(in, dext);
+  const uint32_t dist = dbase + ein_peek(w >> off, dext);
+  ein_drop(in, off + dext);
   if (!INTERIOR) ex = (dom2 && op == isize) ? 2u : ex;
   ex = (dom2 && ex == 0u && dist > op) ? 3u : ex;
   const bool domatch = dom2 && ex == 0u;
@@ -722,12 +718,13 @@ __device__ __forceinline__ uint32_t tok_careful(EIn& in, const HuffP& hl, const 
                                                 const uint8_t* __restrict__ syms_ll,
                                                 const uint8_t* __restrict__ syms_d, TSink& sink,
                                                 uint32_t& op, uint32_t isize) {
-  ein_refill(in);
+  // one window serves the symbol: 15 + 5 + 15 + 13 = 48 bits at most
+  uint64_t w = ein_window(in);
   uint32_t L, idx, hi = 0;
-  if (!huffp_lookup<true>(hl, ein_rev15(in), L, idx, hi)) return ein_avail(in) >= 1u ? 3u : 2u;
+  if (!huffp_lookup<true>(hl, ein_rev15(w), L, idx, hi)) return ein_avail(in) >= 1u ? 3u : 2u;
   if (L > ein_avail(in)) return 2u;
   const uint32_t sym = (uint32_t)syms_ll[idx] | hi;
-  ein_drop(in, L);
+  ein_take(in, w, L);
   if (sym < 256u) {
     if (op == isize) return 2u;
     sink.literal(op++, sym);
@@ -738,19 +735,18 @@ __device__ __forceinline__ uint32_t tok_careful(EIn& in, const HuffP& hl, const 
   uint32_t lbase, lext;
   length_base(sym, lbase, lext);
   if (lext > ein_avail(in)) return 2u;
-  const uint32_t mlen = lbase + ein_peek(in, lext);
-  ein_drop(in, lext);
-  ein_refill(in);
+  const uint32_t mlen = lbase + ein_peek(w, lext);
+  ein_take(in, w, lext);
   uint32_t dh;
-  if (!huffp_lookup<false>(hd, ein_rev15(in), L, idx, dh)) return ein_avail(in) >= 1u ? 3u : 2u;
+  if (!huffp_lookup<false>(hd, ein_rev15(w), L, idx, dh)) return ein_avail(in) >= 1u ? 3u : 2u;
   if (L > ein_avail(in)) return 2u;
   const uint32_t dsym = syms_d[idx];
-  ein_drop(in, L);
+  ein_take(in, w, L);
   if (dsym > 29u) return 3u;
   uint32_t dbase, dext;
   dist_base(dsym, dbase, dext);
   if (dext > ein_avail(in)) return 2u;
-  const uint32_t dist = dbase + ein_peek(in, dext);
+  const uint32_t dist = dbase + ein_peek(w, dext);
   ein_drop(in, dext);
   if (op == isize) return 2u;
   if (dist > op) return 3u;
@@ -759,6 +755,21 @@ __device__ __forceinline__ uint32_t tok_careful(EIn& in, const HuffP& hl, const 
   sink.match(op, n, dist);
   op += n;
   return n < mlen ? 2u : 0u;
+}
+
+// The symbol loop's input step: every TOK_K-th iteration is the wave's epoch.  A bank is 128 bits and
+// comes free only as a whole, so a lane that could not merge at an epoch may hold as few as 129
+// bits, and three wide iterations can use them up before the next epoch: such a lane skips
+// iterations until then (the stall rule).  `need` is what one iteration can read with the block's
+// tables (inflate_tokens_block), not the 64 bits of the widest tables: on the eight generated
+// bodies a lane then skips 0.13 % of its interior iterations (0.30 % with 64).  Giving the short
+// lane an epoch of its own in the iteration in which it runs short skips none, but was measured
+// 1 ms slower at 10 GB than letting it wait: the epoch block, with its wait for the wave's
+// outstanding memory operations, then runs whenever one lane of the 64 is short, far more often
+// than every fourth iteration (profiles/huffman_window/model_iterations.txt, ab.txt section 2).
+__device__ __forceinline__ void tok_epoch(EIn& in, uint32_t& it, uint32_t ex, uint32_t need, int body) {
+  if ((__builtin_amdgcn_readfirstlane(++it) & (TOK_K - 1u)) == 0u) ein_epoch(in);
+  TOK_STALL(ex == 0u && ein_short(in, need), body);
 }
 
 // The symbol loop of one Huffman-coded DEFLATE block; returns the lane's exit code (1 end of block,
@@ -782,7 +793,8 @@ template <bool SPEC>
 __device__ __forceinline__ uint32_t tok_symbols(EIn& in, const HuffP& hl, const HuffP& hd,
                                                 const uint8_t* __restrict__ syms_ll,
                                                 const uint8_t* __restrict__ syms_d, TSink& sink,
-                                                uint32_t& op, uint32_t isize, uint32_t& it, uint32_t interior
+                                                uint32_t& op, uint32_t isize, uint32_t& it, uint32_t interior,
+                                                uint32_t need
 #ifdef HBAM_PROF
                                                 , uint64_t* pt, uint64_t* pc, uint64_t& tq
 #endif
@@ -793,7 +805,7 @@ __device__ __forceinline__ uint32_t tok_symbols(EIn& in, const HuffP& hl, const 
   pd.clear();
   const bool two = SPEC && interior != 0u;
 #define TOK_ANY(c) (__builtin_amdgcn_ballot_w64(c) != 0u)
-#define TOK_INNER (in.total - in.consumed >= TOK_FAST_BITS && op + TOK_ITER_OUT <= isize)
+#define TOK_INNER (in.total - in.cur >= TOK_FAST_BITS && op + TOK_ITER_OUT <= isize)
   for (;;) {
     if (two) {
       while (TOK_ANY(ex == 0u) && !TOK_ANY(ex == 0u && !TOK_INNER)) {
@@ -803,11 +815,11 @@ __device__ __forceinline__ uint32_t tok_symbols(EIn& in, const HuffP& hl, const 
 #ifdef HBAM_PROF
         TOK_PT(2);
 #endif
-        if ((__builtin_amdgcn_readfirstlane(++it) & (TOK_K - 1u)) == 0u) ein_epoch(in);
+        tok_epoch(in, it, ex, need, 2);
 #ifdef HBAM_PROF
         TOK_PT(0);
 #endif
-        if (ex == 0u && !ein_short(in, TOK_FAST_BITS))
+        if (ex == 0u && !ein_short(in, need))
           ex = tok_fast_spec<SPEC, SPEC>(in, fl, fd, syms_ll, syms_d, sink, op, isize, pd);
 #ifdef HBAM_PROF
         TOK_PT(1);
@@ -827,12 +839,12 @@ __device__ __forceinline__ uint32_t tok_symbols(EIn& in, const HuffP& hl, const 
 #ifdef HBAM_PROF
       TOK_PT(2);
 #endif
-      if ((__builtin_amdgcn_readfirstlane(++it) & (TOK_K - 1u)) == 0u) ein_epoch(in);
+      tok_epoch(in, it, ex, need, SPEC ? 1 : 0);
 #ifdef HBAM_PROF
       TOK_PT(0);  // the epoch: merge (waits for the quad in flight) + the next request
 #endif
-      const bool run = ex == 0u && !ein_short(in, TOK_FAST_BITS);
-      const bool fast = in.total - in.consumed >= TOK_FAST_BITS;
+      const bool run = ex == 0u && !ein_short(in, need);
+      const bool fast = in.total - in.cur >= TOK_FAST_BITS;
       if (run && fast) ex = tok_fast_spec<SPEC>(in, fl, fd, syms_ll, syms_d, sink, op, isize, pd);
       if (__builtin_amdgcn_ballot_w64(run && !fast) != 0u) {
         if (run && !fast) {
@@ -880,17 +892,19 @@ __device__ __forceinline__ int32_t inflate_tokens_block(const uint8_t* __restric
     if (last) break;  // stream end
     ein_ensure(in, 64);
     if (ein_avail(in) < 3u) goto leave;
-    last = (in.bb & 1u) != 0;
     {
-      const uint32_t type = (uint32_t)(in.bb >> 1) & 3u;
+      const uint32_t hb = (uint32_t)ein_window(in);
+      last = (hb & 1u) != 0;
+      const uint32_t type = (hb >> 1) & 3u;
       ein_drop(in, 3);
       if (type == 0u) {
-        // stored: byte align, LEN/NLEN, then LEN literal bytes
-        const uint32_t pad = (8u - (in.consumed & 7u)) & 7u;
+        // stored: byte align (the cursor counts from a 16-byte edge, so its low 3 bits are the
+        // phase inside the stream's byte), LEN/NLEN, then LEN literal bytes
+        const uint32_t pad = (8u - (in.cur & 7u)) & 7u;
         ein_drop(in, pad);
         ein_ensure(in, 64);
         if (ein_avail(in) < 32u) goto leave;
-        const uint32_t w = (uint32_t)in.bb;
+        const uint32_t w = (uint32_t)ein_window(in);
         if ((w & 0xffffu) != ((w >> 16) ^ 0xffffu)) { rc = INF_DATA; goto done; }
         ein_drop(in, 32);
         uint32_t len = w & 0xffffu;
@@ -898,9 +912,8 @@ __device__ __forceinline__ int32_t inflate_tokens_block(const uint8_t* __restric
           if (op == isize) goto leave;
           if ((++it & (TOK_K - 1u)) == 0u) ein_epoch(in);
           if (ein_short(in, 8)) { ++len; continue; }  // stall: retry this byte next epoch
-          ein_refill(in);
           if (ein_avail(in) < 8u) goto leave;
-          sink.literal(op++, (uint32_t)in.bb & 0xffu);
+          sink.literal(op++, (uint32_t)ein_window(in) & 0xffu);
           ein_drop(in, 8);
         }
         continue;
@@ -921,9 +934,10 @@ __device__ __forceinline__ int32_t inflate_tokens_block(const uint8_t* __restric
       } else if (type == 2u) {
         ein_ensure(in, 64);
         if (ein_avail(in) < 14u) goto leave;
-        const uint32_t nlen = ((uint32_t)in.bb & 31u) + 257u;
-        const uint32_t ndist = ((uint32_t)(in.bb >> 5) & 31u) + 1u;
-        const uint32_t ncode = ((uint32_t)(in.bb >> 10) & 15u) + 4u;
+        const uint32_t hw = (uint32_t)ein_window(in);
+        const uint32_t nlen = (hw & 31u) + 257u;
+        const uint32_t ndist = ((hw >> 5) & 31u) + 1u;
+        const uint32_t ncode = ((hw >> 10) & 15u) + 4u;
         ein_drop(in, 14);
         if (nlen > 286u || ndist > 30u) { rc = INF_DATA; goto done; }
         // 19 code-length code lengths (3 bits each, RFC 1951 order), at lens[0..19)
@@ -933,13 +947,13 @@ __device__ __forceinline__ int32_t inflate_tokens_block(const uint8_t* __restric
           l4[0] = make_uint4(0, 0, 0, 0);
           l4[1] = make_uint4(0, 0, 0, 0);
         }
-        ein_ensure(in, 64);  // 19 * 3 = 57 bits at most
+        ein_ensure(in, 64);  // 19 * 3 = 57 bits at most: one window
+        uint64_t cw = ein_window(in);
         for (uint32_t i = 0; i < ncode; ++i) {
-          ein_refill(in);
           if (ein_avail(in) < 3u) goto leave;
           const uint32_t o = (uint32_t)((i < 12u ? ord_lo >> (5u * i) : ord_hi >> (5u * (i - 12u))) & 31u);
-          lens[o] = (uint8_t)(in.bb & 7u);
-          ein_drop(in, 3);
+          lens[o] = (uint8_t)(cw & 7u);
+          ein_take(in, cw, 3);
         }
         Huff hc;
         {
@@ -969,13 +983,13 @@ __device__ __forceinline__ int32_t inflate_tokens_block(const uint8_t* __restric
           const bool act = hx == 0u && have < total;
           if (__builtin_amdgcn_ballot_w64(act) == 0u) break;
           if (act && !ein_short(in, 14)) {
-            ein_refill(in);
+            const uint64_t lw = ein_window(in);  // a code (<= 7 bits) and its extra bits (<= 7)
             uint32_t L = 1, sym = 0;
             if (hc.empty) {
               hx = ein_avail(in) < 1u ? 2u : 0u;
             } else {
               int32_t idx;
-              huff_lookup(hc, ein_rev15(in), L, idx);  // CODES sets are complete
+              huff_lookup(hc, ein_rev15(lw), L, idx);  // CODES sets are complete
               if (L > ein_avail(in)) hx = 2u;
               else sym = syms_ll[idx];
             }
@@ -994,8 +1008,9 @@ __device__ __forceinline__ int32_t inflate_tokens_block(const uint8_t* __restric
                   if (sym == 16u && have == 0u) {
                     hx = 3u;
                   } else {
-                    const uint32_t rep = sym == 16u ? 3u + ein_peek(in, 2) : sym == 17u ? 3u + ein_peek(in, 3)
-                                                                                        : 11u + ein_peek(in, 7);
+                    const uint64_t xw = lw >> L;
+                    const uint32_t rep = sym == 16u ? 3u + ein_peek(xw, 2) : sym == 17u ? 3u + ein_peek(xw, 3)
+                                                                                        : 11u + ein_peek(xw, 7);
                     ein_drop(in, xb);
                     if (have + rep > total) {
                       hx = 3u;
@@ -1043,13 +1058,16 @@ __device__ __forceinline__ int32_t inflate_tokens_block(const uint8_t* __restric
     // failed one is not here and so has no say) and a scalar branch; nothing inside the iteration.
     TOK_PT(6);  // header + tables
     {
+      // the most one iteration reads with these tables: two lit/len codes, 5 extra bits, a distance
+      // code, 13 extra bits (63 at the longest codes; TOK_FAST_BITS covers every table)
+      const uint32_t need = 2u * (fit_ll >> TOK_FIT_MAXL) + (fit_d >> TOK_FIT_MAXL) + 18u;
       const uint32_t fit = tok_generic ? 0u : (fit_ll & fit_d);
       const bool mine = (fit & TOK_FIT_LOW) != 0u && (fit_d & TOK_FIT_M11) != 0u;
       uint32_t ex;
 #ifdef HBAM_PROF
-#define TOK_SYMBOLS_ARGS in, hl, hd, syms_ll, syms_d, sink, op, isize, it, tok_interior, pt, pc, tq
+#define TOK_SYMBOLS_ARGS in, hl, hd, syms_ll, syms_d, sink, op, isize, it, tok_interior, need, pt, pc, tq
 #else
-#define TOK_SYMBOLS_ARGS in, hl, hd, syms_ll, syms_d, sink, op, isize, it, tok_interior
+#define TOK_SYMBOLS_ARGS in, hl, hd, syms_ll, syms_d, sink, op, isize, it, tok_interior, need
 #endif
       if (__builtin_amdgcn_ballot_w64(!mine) == 0u) {
         TOK_BODY_ENTERED(1);
@@ -1073,8 +1091,8 @@ done:
   *produced = op;
 #ifdef HBAM_PROF
   // decoder state at exit (tools/diag_inflate_build.py)
-  pc[1] = in.consumed;
-  pc[2] = in.bc | in.nv << 8 | in.rd << 16;
+  pc[1] = in.cur - 8u * ((uint32_t)(uintptr_t)cdata & 15u);  // stream bits consumed
+  pc[2] = in.fill - in.cur;                                   // bits left in the banks
   pc[3] = it;
 #endif
   return rc;

@@ -1,8 +1,10 @@
 """Build an A/B variant of libhbam.so with the product recipe (__graft_entry__.build: the Huffman
 lane pass in its own max-ILP translation unit, everything else default-scheduled) plus extra
 -D flags, into hadoop-bam_amd/NAME.  Never loaded by the tests, smoke() or bench.py unless
-HBAM_LIB names it.
-    python tools/ab_build.py libhbam_k8.so -DHBAM_TOK_K=8"""
+HBAM_LIB names it.  The lane pass's own A/B knobs have been constants since a2116c6: a variant of
+it is built from a second source tree (a checkout of the other commit, with that tree's copy of
+this script); -D flags still reach the switches that are left, such as the profiling build:
+    python tools/ab_build.py libhbam_prof.so -DHBAM_PROF"""
 import os
 import subprocess
 import sys

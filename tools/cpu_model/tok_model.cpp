@@ -17,7 +17,8 @@
 // body, prints the totals, and with -v after the blocks file one line per block
 // (tests/test_tok_spec_model.py).  HBAM_TOK_INTERIOR=0 keeps the specialised loop out of its interior
 // body, as in the library; -i instead of -v adds a second line per block with the loop iterations
-// per body (tests/test_tok_interior_model.py).
+// per body (tests/test_tok_interior_model.py) and a third with the stalled (skipped) iterations among
+// them (tests/test_tok_window_model.py).
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -28,6 +29,8 @@ static uint64_t g_body_entries[2];  // [0] generic, [1] specialised
 #define TOK_BODY_ENTERED(v) (++g_body_entries[v])
 static uint64_t g_body_iters[3];  // [0] generic, [1] specialised, [2] specialised, interior body
 #define TOK_ITER(v) (++g_body_iters[v])
+static uint64_t g_body_stalls[3];  // of those, skipped by the lane for want of bits in its banks (stalls)
+#define TOK_STALL(c, v) ((c) ? (void)++g_body_stalls[v] : (void)0)
 #endif
 #include "inflate_tok.h"
 
@@ -68,7 +71,7 @@ int main(int argc, char** argv) {
   const uint32_t tok_generic = tg && strtol(tg, nullptr, 10) != 0 ? 1u : 0u;
   const char* ti = getenv("HBAM_TOK_INTERIOR");
   const uint32_t tok_interior = ti && strtol(ti, nullptr, 10) == 0 ? 0u : 1u;
-  uint64_t entries[2] = {0, 0}, its[3] = {0, 0, 0};
+  uint64_t entries[2] = {0, 0}, its[3] = {0, 0, 0}, sts[3] = {0, 0, 0};
 #endif
   uint32_t bad = 0, short_ = 0, data = 0;
   uint64_t ubytes = 0;
@@ -167,6 +170,10 @@ int main(int argc, char** argv) {
                (unsigned long long)(g_body_iters[0] - its[0]), (unsigned long long)(g_body_iters[1] - its[1]),
                (unsigned long long)(g_body_iters[2] - its[2]));
         for (int q = 0; q < 3; ++q) its[q] = g_body_iters[q];
+        printf("stalls %u generic %llu specialised %llu interior %llu\n", b,
+               (unsigned long long)(g_body_stalls[0] - sts[0]), (unsigned long long)(g_body_stalls[1] - sts[1]),
+               (unsigned long long)(g_body_stalls[2] - sts[2]));
+        for (int q = 0; q < 3; ++q) sts[q] = g_body_stalls[q];
       }
 #endif
     }
@@ -188,6 +195,10 @@ int main(int argc, char** argv) {
     printf("symbol loop iterations: generic %llu specialised %llu interior %llu\n",
            (unsigned long long)g_body_iters[0], (unsigned long long)g_body_iters[1],
            (unsigned long long)g_body_iters[2]);
+  if (iters)
+    printf("symbol loop stalls: generic %llu specialised %llu interior %llu\n",
+           (unsigned long long)g_body_stalls[0], (unsigned long long)g_body_stalls[1],
+           (unsigned long long)g_body_stalls[2]);
 #endif
   return bad ? 1 : 0;
 }

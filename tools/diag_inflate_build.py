@@ -74,7 +74,7 @@ for lib, var in [(x, v) for x in a.libs for v in a.variants]:
              "isize": int(blocks["isize"][b])}
         if prof is not None:
             e.update(produced=int(P[b, 11]), iters=int(P[b, 24]), consumed=int(P[b, 25]),
-                     bc=int(P[b, 26]) & 0xff, nv=(int(P[b, 26]) >> 8) & 0xff, rd=(int(P[b, 26]) >> 16) & 0xff,
+                     banked=int(P[b, 26]),  # bits left in the banks (fill mark - cursor)
                      it=int(P[b, 27]))
         c0 = int(blocks["coff"][b])
         raw = bytes(data[c0:c0 + int(blocks["clen"][b])])

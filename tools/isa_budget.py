@@ -8,8 +8,8 @@ with line tables:
 Every loop of k_inflate_tokens that holds packed lookups (v_pk_sub_u16) is a symbol loop.  Its basic
 blocks are listed with their instruction counts by unit (VALU / SALU / LDS / VMEM / other) and by
 the source function the line table attributes each instruction to (the innermost inlined frame):
-the lookups (huffp_lookup, ein_rev15), the refills (ein_refill*, ein_sel), the bases
-(length_base*, dist_base*), the packet / mark (TSink, TPend), the epoch (ein_epoch*, ein_short),
+the lookups (huffp_lookup, ein_rev15), the refill (ein_window, ein_align, ein_take: the 64-bit
+window at the bit cursor), the bases (length_base*, dist_base*), the packet / mark (TSink, TPend), the epoch (ein_epoch*, ein_short),
 the token logic of the iteration itself (tok_fast_spec, ein_drop, ein_peek), the careful symbol
 (tok_careful) and the loop's exit bookkeeping (tok_symbols / inflate_tokens_block).  The fast path
 is the straight run of blocks from the loop head to the back edge that holds no tok_careful line;
@@ -21,7 +21,7 @@ category, nothing else.
 import re
 import sys
 
-CATS = [("lookup", r"huffp_lookup|ein_rev15|huffp_fold"), ("refill", r"ein_refill|ein_sel\b"),
+CATS = [("lookup", r"huffp_lookup|ein_rev15|huffp_fold"), ("refill", r"ein_window|ein_align|ein_take"),
         ("bases", r"length_base|dist_base"), ("packet/mark", r"put|mark|mark_if|switch_if|flush|win_store|chunk|literal|match|clear"),
         ("epoch", r"ein_epoch|ein_short|ein_load"), ("token logic", r"tok_fast_spec|ein_drop|ein_peek|ein_avail"),
         ("careful", r"tok_careful"), ("loop", r"tok_symbols|inflate_tokens_block|k_inflate_tokens")]
