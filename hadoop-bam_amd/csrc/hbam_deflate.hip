@@ -24,66 +24,17 @@
 #include <stdint.h>
 
 #include "hbam_internal.h"
+#include "deflate_enc.h"  // the per-thread rules (host and device): hash, match, symbol codes, Huffman, header
 
 namespace hbam {
 
 constexpr uint32_t DF_WG = 256;
 constexpr uint32_t DF_MAXB = 65280;           // largest block accepted (bgzip's 0xff00)
-constexpr uint32_t DF_HBITS = 11;             // 2048-entry hash heads
 constexpr uint32_t DF_SLOT = 65536;           // BGZF member slot (BSIZE <= 65536)
-constexpr uint32_t DF_NSYM = 286 + 30;        // lit/len + distance frequencies per block
-constexpr uint32_t DF_WINDOW = 32768;
-constexpr uint32_t DF_PROBE = 16;             // match bytes verified per position in parallel
-
-__device__ __forceinline__ uint32_t df_hash(uint32_t w) { return (w * 2654435761u) >> (32 - DF_HBITS); }
 
 __device__ __forceinline__ uint32_t df_rd32(const uint8_t* s, uint32_t p) {
   return (uint32_t)s[p] | (uint32_t)s[p + 1] << 8 | (uint32_t)s[p + 2] << 16 | (uint32_t)s[p + 3] << 24;
 }
-// unaligned dword from LDS (the device runs in unaligned access mode, as k_resolve relies on)
-__device__ __forceinline__ uint32_t df_lds32(const uint8_t* s, uint32_t p) { return *(const uint32_t*)(s + p); }
-
-// length of the common prefix of s[a..] and s[p..], at most lim
-__device__ __forceinline__ uint32_t df_match(const uint8_t* s, uint32_t a, uint32_t p, uint32_t lim) {
-  uint32_t l = 0;
-  while (l + 4 <= lim) {
-    const uint32_t x = df_lds32(s, a + l) ^ df_lds32(s, p + l);
-    if (x) return l + (__builtin_ctz(x) >> 3);
-    l += 4;
-  }
-  while (l < lim && s[a + l] == s[p + l]) ++l;
-  return l;
-}
-
-// RFC 1951 length code of a match length 3..258: symbol, extra bits, extra value
-__device__ __forceinline__ void df_len_code(uint32_t len, uint32_t& sym, uint32_t& eb, uint32_t& ev) {
-  if (len == 258) {
-    sym = 285; eb = 0; ev = 0;
-    return;
-  }
-  const uint32_t x = len - 3;
-  if (x < 8) {
-    sym = 257 + x; eb = 0; ev = 0;
-    return;
-  }
-  eb = 31 - __builtin_clz(x) - 2;  // x in [8, 255]: 1..5 extra bits
-  const uint32_t base = (4u + ((x >> eb) & 3u)) << eb;
-  sym = 257 + 4 * eb + 4 + ((x >> eb) & 3u);
-  ev = x - base;
-}
-// distance code of 1..32768
-__device__ __forceinline__ void df_dist_code(uint32_t d, uint32_t& sym, uint32_t& eb, uint32_t& ev) {
-  const uint32_t x = d - 1;
-  if (x < 4) {
-    sym = x; eb = 0; ev = 0;
-    return;
-  }
-  eb = 31 - __builtin_clz(x) - 1;  // x in [4, 32767]: 1..13 extra bits
-  const uint32_t hb = (x >> eb) & 1u;
-  sym = 2 * eb + 2 + hb;
-  ev = x - ((2u + hb) << eb);
-}
-
 #ifdef HBAM_PROF
 __device__ unsigned long long* g_dfprof = nullptr;  // 8 u64 per block (tools/prof_deflate.py)
 #define DF_T() __builtin_amdgcn_s_memtime()
@@ -273,86 +224,6 @@ __global__ __launch_bounds__(DF_WG) void k_lz77_tokens(const uint8_t* __restrict
 #endif
 }
 
-// ---- Huffman code lengths (one thread): Huffman tree by two queues over the symbols sorted
-// by frequency, then lengths limited to maxl.  sorted[] / wt[] / par[] are LDS scratch.
-__device__ void df_lengths(const uint32_t* f, uint32_t n, uint32_t maxl, uint8_t* len,
-                           uint16_t* sorted, uint32_t* wt, uint16_t* par, uint32_t m) {
-  // m = number of used symbols (listed in sorted[0..m) by ascending frequency)
-  for (uint32_t i = 0; i < n; ++i) len[i] = 0;
-  if (m == 0) return;
-  if (m == 1) {
-    len[sorted[0]] = 1;
-    return;
-  }
-  // nodes: 0..m-1 leaves (in sorted order), m..2m-2 internal; two-queue merge
-  for (uint32_t i = 0; i < m; ++i) wt[i] = f[sorted[i]];
-  uint32_t ql = 0, qi = m, ni = m;
-  for (uint32_t k = 0; k < m - 1; ++k) {
-    uint32_t pick[2];
-    for (int j = 0; j < 2; ++j) {
-      if (ql < m && (qi >= ni || wt[ql] <= wt[qi])) pick[j] = ql++;
-      else pick[j] = qi++;
-    }
-    wt[ni] = wt[pick[0]] + wt[pick[1]];
-    par[pick[0]] = (uint16_t)ni;
-    par[pick[1]] = (uint16_t)ni;
-    ++ni;
-  }
-  // depths: root = ni - 1
-  uint32_t* dep = wt;  // reuse: depth of node i (computed top-down: parents have larger ids)
-  dep[ni - 1] = 0;
-  for (int i = (int)ni - 2; i >= 0; --i) dep[i] = dep[par[i]] + 1;
-  // bit-length counts, limited to maxl with zlib's repair step (trees.c gen_bitlen): leaves
-  // deeper than maxl are clamped to maxl, which over-subscribes the code; each repair step
-  // moves a leaf from the deepest level L < maxl down to L+1 and a leaf from maxl up beside
-  // it, lowering the Kraft sum (in units of 2^-maxl) by exactly one.  The step count is the
-  // Kraft excess itself, so the result is complete (inflate rejects incomplete lit/len and
-  // code-length sets).  (r02 counted only the clamped leaves, which under-repairs any
-  // subtree of 4+ leaves below depth maxl: ADVICE r02.)
-  uint32_t cnt[16];
-  for (int L = 0; L < 16; ++L) cnt[L] = 0;
-  for (uint32_t i = 0; i < m; ++i) {
-    const uint32_t d = dep[i];
-    ++cnt[d > maxl ? maxl : d];
-  }
-  uint32_t kraft = 0;
-  for (uint32_t L = 1; L <= maxl; ++L) kraft += cnt[L] << (maxl - L);
-  for (uint32_t excess = kraft - (1u << maxl); excess > 0u && cnt[maxl] > 0u; --excess) {
-    uint32_t L = maxl - 1;
-    while (L > 0 && cnt[L] == 0) --L;
-    if (L == 0) break;  // cannot happen for m <= 2^maxl leaves (guard)
-    --cnt[L];
-    cnt[L + 1] += 2;
-    --cnt[maxl];
-  }
-  // lengths by frequency: the least frequent symbols (front of sorted[]) get the longest codes
-  uint32_t k = 0;
-  for (uint32_t L = maxl; L >= 1; --L)
-    for (uint32_t c = 0; c < cnt[L]; ++c) len[sorted[k++]] = (uint8_t)L;
-}
-
-// canonical codes, bit-reversed for the LSB-first bit stream
-__device__ void df_codes(const uint8_t* len, uint32_t n, uint16_t* code) {
-  uint32_t cnt[16], next[16];
-  for (int L = 0; L < 16; ++L) cnt[L] = 0;
-  for (uint32_t i = 0; i < n; ++i) ++cnt[len[i]];
-  cnt[0] = 0;
-  uint32_t c = 0;
-  for (int L = 1; L < 16; ++L) {
-    c = (c + cnt[L - 1]) << 1;
-    next[L] = c;
-  }
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t L = len[i];
-    if (!L) {
-      code[i] = 0;
-      continue;
-    }
-    const uint32_t v = next[L]++;
-    code[i] = (uint16_t)(__builtin_bitreverse32(v) >> (32 - L));
-  }
-}
-
 // sort used symbols by (frequency, symbol) ascending into sorted[], parallel ranks
 __device__ uint32_t df_sort_used(const uint32_t* f, uint32_t n, uint16_t* sorted, uint32_t t) {
   __shared__ uint32_t s_m;
@@ -370,18 +241,6 @@ __device__ uint32_t df_sort_used(const uint32_t* f, uint32_t n, uint16_t* sorted
   return s_m;
 }
 
-struct DfBits {  // serial bit writer into the LDS image (one thread)
-  uint32_t* w;
-  uint32_t pos;
-  __device__ void put(uint32_t v, uint32_t nb) {
-    if (!nb) return;
-    const uint64_t x = (uint64_t)v << (pos & 31u);
-    w[pos >> 5] |= (uint32_t)x;
-    if ((pos & 31u) + nb > 32u) w[(pos >> 5) + 1] |= (uint32_t)(x >> 32);
-    pos += nb;
-  }
-};
-
 constexpr uint32_t DF_OUTW = (DF_SLOT + 64) / 4;  // LDS image words
 
 __global__ __launch_bounds__(DF_WG) void k_deflate_encode(const uint8_t* __restrict__ src, uint64_t n,
@@ -395,13 +254,13 @@ __global__ __launch_bounds__(DF_WG) void k_deflate_encode(const uint8_t* __restr
   __shared__ uint32_t s_f[DF_NSYM];
   __shared__ uint8_t s_len[DF_NSYM];
   __shared__ uint16_t s_code[DF_NSYM];
-  __shared__ uint16_t s_sorted[320];
-  __shared__ uint32_t s_wt[640];
-  __shared__ uint16_t s_par[640];
+  __shared__ uint16_t s_sorted[DF_SORTED_N];
+  __shared__ uint32_t s_wt[DF_WT_N];
+  __shared__ uint16_t s_par[DF_PAR_N];
   __shared__ uint32_t s_clf[19];
   __shared__ uint8_t s_cll[19];
   __shared__ uint16_t s_clc[19];
-  __shared__ uint16_t s_rle[320];   // RLE'd code lengths: sym | extra << 5
+  __shared__ uint16_t s_rle[DF_RLE_N];  // RLE'd code lengths: sym | extra << 5
   __shared__ uint32_t s_nrle, s_hlit, s_hdist, s_bits, s_wsum[DF_WG / 64];
   const uint32_t b = blockIdx.x, t = threadIdx.x, lane = t & 63u, wv = t >> 6;
   if (b >= nblk) return;
@@ -435,90 +294,27 @@ __global__ __launch_bounds__(DF_WG) void k_deflate_encode(const uint8_t* __restr
   __syncthreads();
   // lit/len lengths
   uint32_t m = df_sort_used(s_f, 286, s_sorted, t);
-  if (t == 0) df_lengths(s_f, 286, 15, s_len, s_sorted, s_wt, s_par, m);
+  if (t == 0) df_lengths(s_f, 286, DF_MAXL_LIT, s_len, s_sorted, s_wt, s_par, m);
   __syncthreads();
   // distance lengths (an empty set is sent as one unused code of length 1)
   m = df_sort_used(s_f + 286, 30, s_sorted, t);
   if (t == 0) {
-    df_lengths(s_f + 286, 30, 15, s_len + 286, s_sorted, s_wt, s_par, m);
+    df_lengths(s_f + 286, 30, DF_MAXL_DIST, s_len + 286, s_sorted, s_wt, s_par, m);
     if (m == 0) s_len[286] = 1;
     df_codes(s_len, 286, s_code);
     df_codes(s_len + 286, 30, s_code + 286);
-    // HLIT / HDIST and the run-length coded length sequence (RFC 1951 3.2.7)
-    uint32_t hlit = 286;
-    while (hlit > 257 && !s_len[hlit - 1]) --hlit;
-    uint32_t hdist = 30;
-    while (hdist > 1 && !s_len[286 + hdist - 1]) --hdist;
+    uint32_t hlit, hdist;
+    s_nrle = df_rle_lengths(s_len, s_rle, s_clf, &hlit, &hdist);
     s_hlit = hlit;
     s_hdist = hdist;
-    for (int i = 0; i < 19; ++i) s_clf[i] = 0;
-    uint32_t nr = 0;
-    const uint32_t tot = hlit + hdist;
-    uint32_t i = 0;
-    while (i < tot) {
-      const uint32_t v = i < hlit ? s_len[i] : s_len[286 + i - hlit];
-      uint32_t r = 1;
-      while (i + r < tot && (i + r < hlit ? s_len[i + r] : s_len[286 + i + r - hlit]) == v) ++r;
-      uint32_t left = r;
-      if (v == 0) {
-        while (left >= 11) {
-          const uint32_t k = left < 138 ? left : 138;
-          s_rle[nr++] = (uint16_t)(18 | (k - 11) << 5);
-          ++s_clf[18];
-          left -= k;
-        }
-        if (left >= 3) {
-          s_rle[nr++] = (uint16_t)(17 | (left - 3) << 5);
-          ++s_clf[17];
-          left = 0;
-        }
-      } else {
-        s_rle[nr++] = (uint16_t)v;
-        ++s_clf[v];
-        --left;
-        while (left >= 3) {
-          const uint32_t k = left < 6 ? left : 6;
-          s_rle[nr++] = (uint16_t)(16 | (k - 3) << 5);
-          ++s_clf[16];
-          left -= k;
-        }
-      }
-      while (left) {
-        s_rle[nr++] = (uint16_t)v;
-        ++s_clf[v];
-        --left;
-      }
-      i += r;
-    }
-    s_nrle = nr;
-    // the code-length code must be complete: at least two symbols
-    uint32_t used = 0;
-    for (int k = 0; k < 19; ++k) used += s_clf[k] ? 1u : 0u;
-    if (used < 2) s_clf[s_clf[0] ? 1 : 0] += 1;
   }
   __syncthreads();
   m = df_sort_used(s_clf, 19, s_sorted, t);
   if (t == 0) {
-    df_lengths(s_clf, 19, 7, s_cll, s_sorted, s_wt, s_par, m);
+    df_lengths(s_clf, 19, DF_MAXL_CL, s_cll, s_sorted, s_wt, s_par, m);
     df_codes(s_cll, 19, s_clc);
-    // header
     DfBits bw{s_out, 0};
-    bw.put(1, 1);  // BFINAL
-    bw.put(2, 2);  // dynamic
-    bw.put(s_hlit - 257, 5);
-    bw.put(s_hdist - 1, 5);
-    const uint8_t ord[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-    uint32_t hclen = 19;
-    while (hclen > 4 && !s_cll[ord[hclen - 1]]) --hclen;
-    bw.put(hclen - 4, 4);
-    for (uint32_t k = 0; k < hclen; ++k) bw.put(s_cll[ord[k]], 3);
-    for (uint32_t k = 0; k < s_nrle; ++k) {
-      const uint32_t sy = s_rle[k] & 31u, ex = s_rle[k] >> 5;
-      bw.put(s_clc[sy], s_cll[sy]);
-      if (sy == 16) bw.put(ex, 2);
-      else if (sy == 17) bw.put(ex, 3);
-      else if (sy == 18) bw.put(ex, 7);
-    }
+    df_put_header(bw, s_hlit, s_hdist, s_cll, s_clc, s_rle, s_nrle);
     s_bits = bw.pos;
   }
   __syncthreads();

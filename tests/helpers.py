@@ -67,6 +67,26 @@ def bgzf_pack(u, level=5, block=65280):
     return b"".join(out)
 
 
+def bgzf_members(comp):
+    """Walk BGZF members -> list of (inflated bytes, isize, crc_ok, bsize)."""
+    import struct
+    import zlib
+    comp = bytes(comp)
+    out, p = [], 0
+    while p < len(comp):
+        assert comp[p:p + 4] == b"\x1f\x8b\x08\x04"
+        assert comp[p + 10:p + 16] == b"\x06\x00BC\x02\x00"
+        bs = struct.unpack_from("<H", comp, p + 16)[0] + 1
+        crc, isz = struct.unpack_from("<II", comp, p + bs - 8)
+        d = zlib.decompressobj(-15)
+        u = d.decompress(comp[p + 18:p + bs - 8])
+        assert d.eof and not d.unused_data
+        out.append((u, isz, zlib.crc32(u) == crc, bs))
+        p += bs
+    assert p == len(comp)
+    return out
+
+
 def bam_stream(data):
     """inflated stream of a whole BAM (zlib)"""
     import struct
