@@ -227,6 +227,16 @@ enum BufId {
   B_ST_DEFERRED,
   B_ST_SMALL,
   B_ST_TEXT,
+  // FASTQ / QSEQ (hbam_fastq.hip)
+  B_FQ_CAND,
+  B_FQ_OUT,
+  B_FQ_SMALL,
+  B_FQ_SMALL2,
+  B_FQ_STOP,
+  B_FQ_SCAN,
+  B_FQ_KEY,
+  B_FQ_SEQ,
+  B_FQ_QUAL,
   B_COUNT_ALL
 };
 
@@ -2694,3 +2704,4 @@ extern "C" int64_t hbam_bgzf_compress(hbam_ctx* c, const uint8_t* src, int src_o
 #include "hbam_vcf.hip"
 #include "hbam_sam.hip"
 #include "hbam_samtext.hip"
+#include "hbam_fastq.hip"

@@ -22,3 +22,6 @@ from .sam import (  # noqa: F401
 from .sam_text import (  # noqa: F401
     AnySAMOutputFormat, KeyIgnoringAnySAMOutputFormat, KeyIgnoringSAMRecordWriter, SAMRecordWriter,
     java_float_to_string, render_record, view)
+from .fastq import (  # noqa: F401
+    FastqInputFormat, FastqRecordReader, FormatConstants, FormatException, NumberFormatException,
+    QseqInputFormat, QseqRecordReader, SequencedFragment)

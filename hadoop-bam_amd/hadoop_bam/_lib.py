@@ -31,6 +31,9 @@ HBAM_ETRIBBLE = -14
 HBAM_ERUNTIME = -15
 HBAM_ENULL = -16
 HBAM_ECLASSCAST = -17
+HBAM_ESEQFORMAT = -18
+HBAM_ENUMBER = -19
+HBAM_QUAL_SANGER, HBAM_QUAL_ILLUMINA = 0, 1
 
 CODE_NAMES = {
     HBAM_OK: "OK", HBAM_EIO: "IOException", HBAM_ETRUNC: "FileTruncatedException",
@@ -41,6 +44,7 @@ CODE_NAMES = {
     HBAM_EMORE: "NeedMoreData", HBAM_EINDEX: "IndexOutOfBoundsException",
     HBAM_ETRIBBLE: "TribbleException", HBAM_ERUNTIME: "RuntimeException",
     HBAM_ENULL: "NullPointerException", HBAM_ECLASSCAST: "ClassCastException",
+    HBAM_ESEQFORMAT: "FormatException", HBAM_ENUMBER: "NumberFormatException",
 }
 
 # every entry point include/hbam.h declares (checked by tests/test_abi.py)
@@ -64,6 +68,7 @@ EXPORTS = [
     "hbam_bai_bound", "hbam_bai_build", "hbam_overlap_filter",
     "hbam_vcf_decode_split", "hbam_vcf_columns_to_host", "hbam_vcf_release", "hbam_vcf_gather_lines",
     "hbam_sam_decode_split", "hbam_sam_render",
+    "hbam_fastq_decode_split", "hbam_qseq_decode_split", "hbam_frag_columns_to_host", "hbam_frag_release",
 ]
 
 # hbam_read_fn: int64_t read(void* user, uint64_t offset, uint64_t len, uint8_t* dst)
@@ -174,6 +179,25 @@ class SamTextC(C.Structure):
         ("text_len", C.c_uint64), ("text", C.c_void_p), ("line_off", C.c_void_p), ("n_deferred", C.c_uint64),
         ("deferred", C.c_void_p),
     ]
+
+
+class FragColumnsC(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("status", C.c_int32), ("host", C.c_int32), ("err_pos", C.c_uint64),
+                ("first_pos", C.c_uint64), ("end_pos", C.c_uint64)] + \
+               [(k, C.c_void_p) for k in ("rec_off", "pos_after", "present", "run", "lane", "tile", "xpos", "ypos",
+                                          "read", "filter_passed", "control", "instrument", "flowcell", "index",
+                                          "key_off", "seq_off", "qual_off", "key", "seq", "qual")] + \
+               [("key_len", C.c_uint64), ("seq_len", C.c_uint64), ("qual_len", C.c_uint64),
+                ("text_base", C.c_uint64)]
+
+
+# SequencedFragment's *_Present bits, in hbam_frag_columns.present's order
+FRAG_PRESENT = {"instrument": 0x001, "run": 0x002, "flowcell": 0x004, "lane": 0x008, "tile": 0x010,
+                "xpos": 0x020, "ypos": 0x040, "read": 0x080, "filter_passed": 0x100, "control": 0x200,
+                "index": 0x400}
+FRAG_FIELDS = [("rec_off", np.uint64), ("pos_after", np.uint64), ("present", np.uint32), ("run", np.int32),
+               ("lane", np.int32), ("tile", np.int32), ("xpos", np.int32), ("ypos", np.int32),
+               ("read", np.int32), ("filter_passed", np.int32), ("control", np.int32)]
 
 
 VCF_FIELDS = [("line_off", np.uint64), ("line_len", np.uint32), ("chrom", np.int32), ("pos", np.int32),
@@ -296,6 +320,12 @@ def load(path=None):
                                             C.c_uint64, C.c_uint64, vp, C.c_uint32, vp, C.c_uint64, C.c_int32,
                                             C.POINTER(Columns)]),
         "hbam_sam_render": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_int, vp, vp, C.c_int32, C.POINTER(SamTextC)]),
+        "hbam_fastq_decode_split": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+                                              C.c_uint64, C.c_int32, C.c_int32, C.POINTER(FragColumnsC)]),
+        "hbam_qseq_decode_split": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+                                             C.c_uint64, C.c_int32, C.c_int32, C.POINTER(FragColumnsC)]),
+        "hbam_frag_columns_to_host": (C.c_int, [vp, C.POINTER(FragColumnsC), C.POINTER(FragColumnsC)]),
+        "hbam_frag_release": (None, [vp, C.POINTER(FragColumnsC)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name, None)
@@ -1001,6 +1031,54 @@ class Context:
             out[name] = arr(getattr(h, name), k, dt)
         out["tab"] = arr(h.tab, 8 * k, np.uint32).reshape(k, 8)
         self.L.hbam_vcf_release(self.h, C.byref(h))
+        out["timing"] = self.timing()
+        return out
+
+    # ---- FASTQ / QSEQ (hbam_fastq.hip) ------------------------------------------------------------
+    def frag_decode_split_device(self, fmt, data, start, length, encoding=HBAM_QUAL_SANGER, filter_failed_qc=False,
+                                 text_base=0, file_len=None):
+        """hbam_fastq_decode_split (fmt "fastq") / hbam_qseq_decode_split ("qseq") -> (rc, device
+        FragColumnsC).  length None = the reference's unbounded end (a compressed file)."""
+        p, n, dev, keep = self._ptr(data)
+        if file_len is None:
+            file_len = text_base + n
+        fn = {"fastq": self.L.hbam_fastq_decode_split, "qseq": self.L.hbam_qseq_decode_split}[fmt]
+        d = FragColumnsC()
+        rc = fn(self.h, p, dev, int(text_base), n, int(file_len), int(start),
+                0xffffffffffffffff if length is None else int(length), int(encoding), int(bool(filter_failed_qc)),
+                C.byref(d))
+        return rc, d
+
+    def frag_decode_split(self, fmt, data, start, length, encoding=HBAM_QUAL_SANGER, filter_failed_qc=False,
+                          text_base=0, file_len=None):
+        """FastqRecordReader / QseqRecordReader over one split -> host numpy columns: n, status, err_pos,
+        first_pos, end_pos, FRAG_FIELDS, instrument / flowcell / index as (n, 2) offset-length pairs
+        into the window, and the pools key / seq / qual with their n + 1 offsets."""
+        rc, d = self.frag_decode_split_device(fmt, data, start, length, encoding, filter_failed_qc, text_base,
+                                              file_len)
+        if rc:
+            return {"rc": rc, "error": self.last_error()}
+        h = FragColumnsC()
+        rc = self.L.hbam_frag_columns_to_host(self.h, C.byref(d), C.byref(h))
+        if rc:
+            return {"rc": rc, "error": self.last_error()}
+        k = int(h.n)
+        out = {"rc": 0, "n": k, "status": int(h.status), "err_pos": int(h.err_pos), "first_pos": int(h.first_pos),
+               "end_pos": int(h.end_pos)}
+
+        def arr(ptr, count, dt):
+            if not count:
+                return np.zeros(0, dt)
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)),
+                                         shape=(count * np.dtype(dt).itemsize,)).view(dt).copy()
+        for name, dt in FRAG_FIELDS:
+            out[name] = arr(getattr(h, name), k, dt)
+        for name in ("instrument", "flowcell", "index"):
+            out[name] = arr(getattr(h, name), 2 * k, np.uint32).reshape(k, 2)
+        for name in ("key", "seq", "qual"):
+            out[name + "_off"] = arr(getattr(h, name + "_off"), k + 1, np.uint64)
+            out[name] = arr(getattr(h, name), int(getattr(h, name + "_len")), np.uint8)
+        self.L.hbam_frag_release(self.h, C.byref(h))
         out["timing"] = self.timing()
         return out
 

@@ -50,12 +50,21 @@ class ClassCastException(TypeError):
     pass
 
 
+class FormatException(RuntimeError):
+    """org.seqdoop.hadoop_bam.FormatException (FormatException.java: a RuntimeException)."""
+
+
+class NumberFormatException(IllegalArgumentException):
+    """java.lang.NumberFormatException (Integer.parseInt)."""
+
+
 _EXC = {
     _lib.HBAM_EIO: IOException, _lib.HBAM_ETRUNC: FileTruncatedException,
     _lib.HBAM_EFORMAT: SAMFormatException, _lib.HBAM_ERUNTIMEIO: RuntimeIOException,
     _lib.HBAM_EEOF: RuntimeEOFException, _lib.HBAM_EREFID: IllegalArgumentException,
     _lib.HBAM_EDATA: JavaRuntimeException, _lib.HBAM_ENULL: NullPointerException,
     _lib.HBAM_ECLASSCAST: ClassCastException,
+    _lib.HBAM_ESEQFORMAT: FormatException, _lib.HBAM_ENUMBER: NumberFormatException,
 }
 
 

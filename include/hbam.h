@@ -20,9 +20,12 @@
  *                     NullPointerException after VCFCodec.decode returns null (text VCF)
  *   HBAM_ENULL        NullPointerException (multi-input Sort's group rewrite, cli/Utils.java:316-323)
  *   HBAM_ECLASSCAST   ClassCastException (an RG / PG attribute that is not a string)
+ *   HBAM_ESEQFORMAT   org.seqdoop.hadoop_bam.FormatException (FASTQ, QSEQ)
+ *   HBAM_ENUMBER      NumberFormatException (Integer.parseInt in the FASTQ / QSEQ readers)
  *
  * Library-specific codes (no reference counterpart): HBAM_ENOMEM, HBAM_EUNSUPPORTED
- * (BGZF block with ISIZE > 65536; SAM text the encoder does not restate), HBAM_EDEVICE (HIP
+ * (BGZF block with ISIZE > 65536; SAM text the encoder does not restate; the FASTQ / QSEQ inputs
+ * listed at hbam_fastq_decode_split), HBAM_EDEVICE (HIP
  * error), HBAM_EINVAL, HBAM_EMORE
  * (the compressed window handed in ends before the split's last record).
  *
@@ -63,6 +66,8 @@ extern "C" {
 #define HBAM_ERUNTIME (-15) /* another RuntimeException escaping BCF2Codec.decode (restated, unpinned) */
 #define HBAM_ENULL (-16) /* NullPointerException (cli/Utils.java:316-323: a group lookup without a table) */
 #define HBAM_ECLASSCAST (-17) /* ClassCastException ((String) of a non-string RG / PG attribute) */
+#define HBAM_ESEQFORMAT (-18) /* FormatException (FormatException.java): QSEQ field count, base quality range */
+#define HBAM_ENUMBER (-19) /* NumberFormatException out of Integer.parseInt (FASTQ Illumina id, QSEQ ints) */
 
 typedef struct hbam_ctx hbam_ctx;
 
@@ -786,6 +791,126 @@ typedef struct hbam_sam_text {
 int hbam_sam_render(hbam_ctx* ctx, const uint8_t* ubuf, const uint64_t* rec_off, const uint32_t* perm,
                     uint64_t n, int on_device, const uint8_t* names, const uint32_t* name_off,
                     int32_t n_ref, hbam_sam_text* out);
+
+/* ---- FASTQ and QSEQ: FastqInputFormat / FastqRecordReader (FastqInputFormat.java:56-393) and
+ * QseqInputFormat / QseqRecordReader (QseqInputFormat.java:58-429) over one FileSplit -------------
+ * Both fill SequencedFragment values (SequencedFragment.java).  The line rule is the reference's own
+ * LineReader.readLine (LineReader.java:111-173): '\n', a lone '\r' and "\r\n" all end a line, the end
+ * of the file ends an unterminated one, and a line exists iff it consumes at least one byte.
+ *
+ * Output: device memory owned by the context, valid until the next hbam_fastq_decode_split /
+ * hbam_qseq_decode_split on it (host = 0); after hbam_frag_columns_to_host host arrays owned by the
+ * caller (host = 1), freed by hbam_frag_release.  Record i's key is key[key_off[i], key_off[i + 1]),
+ * likewise seq and qual: the pools hold the bytes the reference hands out (qualities as Phred+33,
+ * QSEQ bases with '.' as 'N').  instrument / flowcell / index are (offset, length) pairs, two u32 per
+ * record, the offset relative to the window's first byte (file offset text_base); a QSEQ index
+ * sequence is the raw field: its '.' -> 'N' replacement is the caller's.  present is the mask of
+ * non-null fields in SequencedFragment's own bit order (Instrument 0x1, RunNumber 0x2, FlowcellId 0x4,
+ * Lane 0x8, Tile 0x10, Xpos 0x20, Ypos 0x40, Read 0x80, FilterPassed 0x100, ControlNumber 0x200,
+ * IndexSequence 0x400); a column whose bit is clear holds no meaning. */
+#define HBAM_QUAL_SANGER 0   /* "sanger": Phred+33, checked against [33, 126] */
+#define HBAM_QUAL_ILLUMINA 1 /* "illumina": Phred+64, checked against [64, 126] and rewritten as byte - 31 */
+typedef struct hbam_frag_columns {
+  uint64_t n;          /* records returned before `status` (records the QC filter drops are not counted) */
+  int32_t status;      /* HBAM_OK, the exception next() raises after n records, or HBAM_EMORE */
+  int32_t host;
+  uint64_t err_pos;    /* status != HBAM_OK: the file offset the reference's position message carries */
+  uint64_t first_pos;  /* getPos() before the first next(): where positionAtFirstRecord leaves the reader */
+  uint64_t end_pos;    /* getPos() after the next() that ends the split (returns false, or raises) */
+  uint64_t* rec_off;   /* file offset of the record's first byte */
+  uint64_t* pos_after; /* getPos() after the next() that returns this record */
+  uint32_t* present;
+  int32_t* run;
+  int32_t* lane;
+  int32_t* tile;
+  int32_t* xpos;
+  int32_t* ypos;
+  int32_t* read;
+  int32_t* filter_passed; /* 0 / 1 */
+  int32_t* control;
+  uint32_t* instrument; /* u32[2n]: offset into the window, length */
+  uint32_t* flowcell;
+  uint32_t* index;
+  uint64_t* key_off;   /* u64[n + 1] */
+  uint64_t* seq_off;
+  uint64_t* qual_off;
+  uint8_t* key;
+  uint8_t* seq;
+  uint8_t* qual;
+  uint64_t key_len;    /* bytes in each pool */
+  uint64_t seq_len;
+  uint64_t qual_len;
+  uint64_t text_base;
+} hbam_frag_columns;
+
+/* FastqRecordReader over FileSplit [start, start + length) of an uncompressed FASTQ file of file_len
+ * bytes (a gzip file: the caller inflates it and passes start = 0 and length = UINT64_MAX, the
+ * reference's end = Long.MAX_VALUE).  text = file bytes [text_base, text_base + text_len), a window of
+ * at most 2 GiB (HBAM_EINVAL above) with text_base <= start, under hbam_vcf_decode_split's alignment
+ * contract.  encoding = HBAM_QUAL_*; filter_failed_qc != 0 drops records whose filterPassed is false.
+ *
+ * Positioning (positionAtFirstRecord, :158-200).  start == 0: first_pos = 0, nothing is checked.
+ * start > 0: the lines are counted from byte `start` itself, and the walk ends at the first line j
+ * that starts below start + length (the walk stores at most min(10000, end - start) bytes of a line:
+ * from the split's end on it stores nothing and sees no '@'), whose first byte is '@' and for which either (a) line j + 2 exists, is not empty and begins with
+ * '+': first_pos = the start of line j; or (b) the file has no line j + 2: the reference's loop ends
+ * there too (its third read returns 0) with the reader at the start of line j + 1 (the file's length
+ * when there is none), which is first_pos.  Without such a line first_pos = file_len.  The walk may
+ * pass start + length; then no record is returned.
+ * Records: record k is lines j + 4k .. j + 4k + 3 from first_pos.  next() returns the record at the
+ * reader's position while that position < start + length, except that its filter loop reads on
+ * behind a dropped record without looking at the position.  skip(1) drops the first byte untested;
+ * the key is the rest of line 0, the sequence line 1, the quality line 3, each stored up to 10000
+ * bytes (the rest is dropped but counted in the position); the lengths of sequence and quality are
+ * not compared.  The first record that raises ends the split, status / err_pos tell how:
+ *   HBAM_ERUNTIME      line 2 is empty or does not begin with '+' (err_pos = the start of line 3);
+ *                      the file ends inside the record, which includes an empty line where a record
+ *                      should start, directly before the end of the file ("unexpected end of file",
+ *                      err_pos = file_len);
+ *   HBAM_ENUMBER       a numeric group of a matching Illumina identifier lies outside int32;
+ *   HBAM_ESEQFORMAT    a stored quality byte outside the encoding's range (a returned record only);
+ *   HBAM_EUNSUPPORTED  an empty line where a record should start, with data behind it (skip(1) eats
+ *                      the terminator and the four-line frame shifts: not restated); a key with a
+ *                      byte >= 0x80 while the reader still looks for Illumina identifiers (the pattern
+ *                      runs on the decoded string: not restated).
+ * Illumina identifier (ILLUMINA_PATTERN, :95, matched against the whole stored key):
+ * ([^:]+):(\d+):([^:]*):(\d+):(\d+):(-?\d+):(-?\d+)\s+([123]):([YN]):(\d+):(.*) with \d = ASCII digits
+ * and \s = space, \t, \x0b, \f.  Records before the first whose key does not match (dropped ones
+ * counted) carry all eleven fields, filter_passed = (group 9 == "N"); that record and every later
+ * one carry only read, and only when the key has at least two bytes and ends in '/' and a digit.
+ * HBAM_EMORE: the window ends (before file_len) inside a record the reader reads, or before the
+ * positioning walk is decided; call again with a longer window.
+ * Timing: scan_ms structural pass, walk_ms line starts and positioning, decode_ms the record passes,
+ * pools_ms scans, compaction and pools, total_ms, ubuf_bytes = text_len, n_records, pool_bytes. */
+int hbam_fastq_decode_split(hbam_ctx* ctx, const uint8_t* text, int on_device, uint64_t text_base,
+                            uint64_t text_len, uint64_t file_len, uint64_t start, uint64_t length,
+                            int32_t encoding, int32_t filter_failed_qc, hbam_frag_columns* out);
+/* QseqRecordReader, the same arguments; the window begins at or before start - 1 (0 for start == 0).
+ * Positioning (:138-157): start > 0 opens at start - 1 and drops the line read there; first_pos = the
+ * start of the next line.  One line is one record, returned while the reader's position < start +
+ * length (and behind a dropped record, as above).  Per line, in this order:
+ *   HBAM_ERUNTIME      the line consumes 20000 bytes or more (err_pos = its start);
+ *   HBAM_ESEQFORMAT    setFieldPositionsAndLengths finds other than 11 fields: its loop ends when it
+ *                      reaches the line's length, so an empty line has 0 fields, the empty field
+ *                      behind a trailing tab is not counted, and fields behind the 11th are ignored
+ *                      (err_pos = the position after the line - the line's length, as the message);
+ *   HBAM_EUNSUPPORTED  a byte >= 0x80 in fields 0-7 (Text.decode is not restated);
+ *   HBAM_ENUMBER       fields 1, 2, 3, 4, 5, 7 (run, lane, tile, x, y, read) are Integer.parseInt:
+ *                      [+-]? digits inside int32;
+ *   HBAM_ESEQFORMAT    a quality byte (field 9) outside the encoding's range, returned records only.
+ * key = fields 0-5 with their tabs as ':', ':' and field 7; filter_passed = (first byte of field 10
+ * != '0'); the index sequence is null when field 6 is not empty and begins with '0'; the sequence is
+ * field 8 with '.' as 'N'.  flowcell and control are never present.
+ * Both positioning walks call readLine(Text, int): the int is maxLineLength (what is stored), not
+ * maxBytesToConsume, so no line of a walk is cut and the positions do not depend on LineReader's
+ * buffer size. */
+int hbam_qseq_decode_split(hbam_ctx* ctx, const uint8_t* text, int on_device, uint64_t text_base,
+                           uint64_t text_len, uint64_t file_len, uint64_t start, uint64_t length,
+                           int32_t encoding, int32_t filter_failed_qc, hbam_frag_columns* out);
+/* host copy of the n records' columns and the three pools */
+int hbam_frag_columns_to_host(hbam_ctx* ctx, const hbam_frag_columns* dev, hbam_frag_columns* host);
+/* frees a host copy's arrays; clears the struct either way */
+void hbam_frag_release(hbam_ctx* ctx, hbam_frag_columns* cols);
 
 #ifdef __cplusplus
 }
