@@ -1068,6 +1068,89 @@ float ev_ms(hbam_ctx* c, int a, int b) {
   return ms;
 }
 
+// The record tail of every decode that ends in hbam_columns (BAM, SAM text), after k_decode_fixed:
+// the four pool scans in one pass (k_scan4_*), their totals read back in one round trip, the pools,
+// k_decode_pools between events 7 and 8.  also_read: a device word of the caller's read back in
+// that round trip (into pinned_small[PS_ALSO_READ]): k_decode_fixed's first stop where the caller
+// has not read it yet (SAM text), and a stop below n there ends the call before the pools.
+constexpr int PS_POOL_TOTALS = 96, PS_ALSO_READ = 100;
+int finish_pools(hbam_ctx* c, const uint8_t* ub, uint64_t n, const uint64_t* rec_off, DevColumns& dc,
+                 const uint64_t* also_read = nullptr) {
+  int rc;
+  {
+    const uint32_t tiles = (uint32_t)std::max<uint64_t>(1, (n + SCAN4_TILE - 1) / SCAN4_TILE);
+    uint64_t* partial;
+    if ((rc = ensure(c, B_PARTIAL, 4ull * tiles + 1, &partial))) return rc;
+    const Scan4In in{{dc.name_len, dc.cigar_n, dc.seq_len, dc.aux_len}};
+    const Scan4Out so{{dc.name_off, dc.cigar_off, dc.seq_off, dc.aux_off}};
+    k_scan4_reduce<<<tiles, 256, 0, c->stream>>>(in, n, partial, tiles);
+    k_scan4_partials<<<4, 256, 0, c->stream>>>(partial, tiles, so, n);
+    k_scan4_apply<<<tiles, 256, 0, c->stream>>>(in, n, partial, tiles, so);
+    HIPCHK(c, hipGetLastError());
+  }
+  const uint64_t* offs[4] = {dc.name_off, dc.cigar_off, dc.seq_off, dc.aux_off};
+  for (int q = 0; q < 4; ++q)
+    HIPCHK(c, hipMemcpyAsync(c->pinned_small + PS_POOL_TOTALS + q, offs[q] + n, 8, hipMemcpyDeviceToHost, c->stream));
+  if (also_read)
+    HIPCHK(c, hipMemcpyAsync(c->pinned_small + PS_ALSO_READ, also_read, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t tot_name = c->pinned_small[PS_POOL_TOTALS], tot_cig = c->pinned_small[PS_POOL_TOTALS + 1],
+                 tot_seq = c->pinned_small[PS_POOL_TOTALS + 2], tot_aux = c->pinned_small[PS_POOL_TOTALS + 3];
+  if (also_read && c->pinned_small[PS_ALSO_READ] < n)  // k_decode_fixed stops at no record the encoder wrote
+    return set_err(c, HBAM_EDEVICE, "hbam_sam_decode_split: record %llu does not decode",
+                   (unsigned long long)c->pinned_small[PS_ALSO_READ]);
+  if ((rc = ensure(c, B_C_NAMES, tot_name + 1, &dc.names))) return rc;
+  if ((rc = ensure(c, B_C_CIGARS, tot_cig + 1, &dc.cigars))) return rc;
+  if ((rc = ensure(c, B_C_SEQ, tot_seq + 1, &dc.seq))) return rc;
+  if ((rc = ensure(c, B_C_QUAL, tot_seq + 1, &dc.qual))) return rc;
+  if ((rc = ensure(c, B_C_AUX, tot_aux + 1, &dc.aux))) return rc;
+  HIPCHK(c, hipEventRecord(c->ev[7], c->stream));
+  if (n)
+    k_decode_pools<<<(uint32_t)std::min<uint64_t>(grid_for(n, 256), POOLS_MAX_WG), 256, 0, c->stream>>>(ub, n, rec_off,
+                                                                                                       dc);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(c->ev[8], c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->timing.pools_ms = ev_ms(c, 7, 8);
+  c->timing.pool_bytes = tot_name + 4 * tot_cig + 2 * tot_seq + tot_aux;
+  return HBAM_OK;
+}
+
+// DevColumns -> the ABI struct: the one place that maps them
+void columns_out(hbam_columns* out, const DevColumns& dc, uint64_t* voff, uint64_t* rec_off, uint8_t* ub,
+                 uint64_t utotal, uint64_t n, int32_t status, uint64_t err_rec) {
+  out->n_records = n;
+  out->status = status;
+  out->err_record = err_rec;
+  out->voffset = voff;
+  out->key = dc.key;
+  out->rec_off = rec_off;
+  out->ubuf = ub;
+  out->ubuf_len = utotal;
+  out->block_size = dc.block_size;
+  out->ref_id = dc.ref_id;
+  out->pos = dc.pos;
+  out->l_read_name = dc.l_read_name;
+  out->mapq = dc.mapq;
+  out->bin = dc.bin;
+  out->n_cigar = dc.n_cigar;
+  out->flag = dc.flag;
+  out->l_seq = dc.l_seq;
+  out->next_ref_id = dc.next_ref_id;
+  out->next_pos = dc.next_pos;
+  out->tlen = dc.tlen;
+  out->layout_ok = dc.layout_ok;
+  out->name_off = dc.name_off;
+  out->names = dc.names;
+  out->cigar_off = dc.cigar_off;
+  out->cigars = dc.cigars;
+  out->seq_off = dc.seq_off;
+  out->seq = dc.seq;
+  out->qual = dc.qual;
+  out->aux_off = dc.aux_off;
+  out->aux = dc.aux;
+}
+
 }  // namespace
 
 extern "C" int hbam_decode_split(hbam_ctx* c, const uint8_t* comp, int on_device,
@@ -1312,72 +1395,8 @@ extern "C" int hbam_decode_split(hbam_ctx* c, const uint8_t* comp, int on_device
     if (n_final >= nrec) HIPCHK(c, copy_sync(c, voff + n_final, &v_start, 8, hipMemcpyHostToDevice));
   }
   // ---- pools
-  uint64_t tot_name = 0, tot_cig = 0, tot_seq = 0, tot_aux = 0;
-  // the four pool scans in one pass (k_scan4_*), their totals read back in one round trip
-  {
-    const uint32_t tiles = (uint32_t)std::max<uint64_t>(1, (n_final + SCAN4_TILE - 1) / SCAN4_TILE);
-    uint64_t* partial;
-    if ((rc = ensure(c, B_PARTIAL, 4ull * tiles + 1, &partial))) return rc;
-    const Scan4In in{{dc.name_len, dc.cigar_n, dc.seq_len, dc.aux_len}};
-    const Scan4Out so{{dc.name_off, dc.cigar_off, dc.seq_off, dc.aux_off}};
-    k_scan4_reduce<<<tiles, 256, 0, c->stream>>>(in, n_final, partial, tiles);
-    k_scan4_partials<<<4, 256, 0, c->stream>>>(partial, tiles, so, n_final);
-    k_scan4_apply<<<tiles, 256, 0, c->stream>>>(in, n_final, partial, tiles, so);
-    HIPCHK(c, hipGetLastError());
-  }
-  {
-    const uint64_t* offs[4] = {dc.name_off, dc.cigar_off, dc.seq_off, dc.aux_off};
-    for (int q = 0; q < 4; ++q)
-      HIPCHK(c, hipMemcpyAsync(c->pinned_small + 96 + q, offs[q] + n_final, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    tot_name = c->pinned_small[96];
-    tot_cig = c->pinned_small[97];
-    tot_seq = c->pinned_small[98];
-    tot_aux = c->pinned_small[99];
-  }
-  if ((rc = ensure(c, B_C_NAMES, tot_name + 1, &dc.names))) return rc;
-  if ((rc = ensure(c, B_C_CIGARS, tot_cig + 1, &dc.cigars))) return rc;
-  if ((rc = ensure(c, B_C_SEQ, tot_seq + 1, &dc.seq))) return rc;
-  if ((rc = ensure(c, B_C_QUAL, tot_seq + 1, &dc.qual))) return rc;
-  if ((rc = ensure(c, B_C_AUX, tot_aux + 1, &dc.aux))) return rc;
-  HIPCHK(c, hipEventRecord(c->ev[7], c->stream));
-  if (n_final)
-    k_decode_pools<<<(uint32_t)std::min<uint64_t>(grid_for(n_final, 256), POOLS_MAX_WG), 256, 0, c->stream>>>(
-        ub, n_final, rec_off, dc);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(c->ev[8], c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-
-  out->n_records = n_final;
-  out->status = status;
-  out->err_record = err_rec;
-  out->voffset = voff;
-  out->key = dc.key;
-  out->rec_off = rec_off;
-  out->ubuf = ub;
-  out->ubuf_len = utotal;
-  out->block_size = dc.block_size;
-  out->ref_id = dc.ref_id;
-  out->pos = dc.pos;
-  out->l_read_name = dc.l_read_name;
-  out->mapq = dc.mapq;
-  out->bin = dc.bin;
-  out->n_cigar = dc.n_cigar;
-  out->flag = dc.flag;
-  out->l_seq = dc.l_seq;
-  out->next_ref_id = dc.next_ref_id;
-  out->next_pos = dc.next_pos;
-  out->tlen = dc.tlen;
-  out->layout_ok = dc.layout_ok;
-  out->name_off = dc.name_off;
-  out->names = dc.names;
-  out->cigar_off = dc.cigar_off;
-  out->cigars = dc.cigars;
-  out->seq_off = dc.seq_off;
-  out->seq = dc.seq;
-  out->qual = dc.qual;
-  out->aux_off = dc.aux_off;
-  out->aux = dc.aux;
+  if ((rc = finish_pools(c, ub, n_final, rec_off, dc))) return rc;
+  columns_out(out, dc, voff, rec_off, ub, utotal, n_final, status, err_rec);
 
   c->timing.scan_ms = ev_ms(c, 0, 1);
   c->timing.inflate_ms = ev_ms(c, 2, 3);
@@ -1385,13 +1404,11 @@ extern "C" int hbam_decode_split(hbam_ctx* c, const uint8_t* comp, int on_device
   c->timing.resolve_ms = ev_ms(c, 11, 3);
   c->timing.walk_ms = ev_ms(c, 4, 5);
   c->timing.decode_ms = ev_ms(c, 5, 6);
-  c->timing.pools_ms = ev_ms(c, 7, 8);
   c->timing.total_ms = ev_ms(c, 0, 8);
   c->timing.n_blocks = nb;
   c->timing.comp_bytes = ch.end_pos - start;
   c->timing.ubuf_bytes = utotal;
   c->timing.n_records = n_final;
-  c->timing.pool_bytes = tot_name + 4 * tot_cig + 2 * tot_seq + tot_aux;
   return HBAM_OK;
 }
 
@@ -2701,6 +2718,7 @@ extern "C" int64_t hbam_bgzf_compress(hbam_ctx* c, const uint8_t* src, int src_o
 #include "hbam_bcf_api.hip"
 #include "hbam_comm.hip"
 #include "hbam_bai.hip"
+#include "hbam_lines.hip"
 #include "hbam_vcf.hip"
 #include "hbam_sam.hip"
 #include "hbam_samtext.hip"

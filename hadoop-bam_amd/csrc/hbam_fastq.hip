@@ -1,18 +1,13 @@
 // hbam_fastq.hip — FASTQ and QSEQ on the device: FastqRecordReader (FastqInputFormat.java:56-393) and
 // QseqRecordReader (QseqInputFormat.java:58-429) over one FileSplit, both filling SequencedFragment
 // columns.  Included at the end of hbam_capi.hip (it uses that file's buffers, scan and staging
-// helpers, hbam_vcf.hip's byte masks, k_vcf_starts and vcf_parse_int, and the Sort path's unit
+// helpers, hbam_lines.hip's front end, hbam_vcf.hip's vcf_parse_int, and the Sort path's unit
 // gather).  gfx950, wave64.
 //
-//   k_seq_scan        structural pass, k_vcf_scan's shape (a lane per 16 aligned bytes, a wave per
-//                     4 KiB tile) under LineReader.readLine's line rule (LineReader.java:111-173):
-//                     LF, a lone CR and CRLF all end a line.  Bit i of the line-end bitmap is set
-//                     iff b[i] == '\n', or b[i] == '\r' and the byte after it is not '\n': the bit
-//                     marks the LAST byte of a terminator, so k_vcf_starts works on it unchanged.
-//                     The byte after a quad is one more load (it crosses quad, step, tile and window
-//                     boundaries alike); the byte after the window is "not LF" at the end of the
-//                     file and "LF" before it (a CR there stays open: the line is incomplete).
-//   (scan_exclusive, k_vcf_starts)   line counts per tile -> the start offset of every line.
+//   k_line_scan<true, false> (FASTQ), <true, true> (QSEQ, with the tab bitmap), (scan_exclusive),
+//   k_vcf_starts      the structural pass under LineReader.readLine's line rule (LF, a lone CR and
+//                     CRLF all end a line) and the start offset of every line: text_lines
+//                     (hbam_lines.hip).
 //   k_fq_stop         FASTQ positioning (positionAtFirstRecord, :158-200) as a per-line predicate and
 //                     a min-reduction: the first '@' line below the split's end whose line + 2 is a
 //                     non-empty '+' line, or (the walk's other exit) whose line + 2 does not exist.
@@ -69,41 +64,6 @@ struct FragOut {
   uint64_t* off[3];
   uint64_t* src[3];
 };
-
-__global__ __launch_bounds__(VCF_WG) void k_seq_scan(const uint8_t* __restrict__ text16, uint32_t end, uint32_t q0,
-                                                     uint32_t ntiles, uint32_t tail_lf, uint32_t want_tabs,
-                                                     uint16_t* __restrict__ nlmap, uint16_t* __restrict__ tabmap,
-                                                     uint32_t* __restrict__ count) {
-  const uint32_t wave = blockIdx.x * (VCF_WG / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-  if (wave >= ntiles) return;  // wave-uniform
-  uint32_t cnt = 0;
-#pragma unroll
-  for (uint32_t s = 0; s < VCF_STEPS; ++s) {
-    const uint64_t b = (uint64_t)wave * VCF_TILE + s * 1024u + lane * 16u;
-    uint32_t nl = 0, tb = 0;
-    if (b < end) {
-      const uint4 q = *reinterpret_cast<const uint4*>(text16 + b);
-      // the byte after the quad: inside the window a load, behind it the caller's answer
-      const bool next_lf = b + 16 < end ? text16[b + 16] == '\n' : tail_lf != 0;
-      const uint32_t hi = (uint32_t)min((uint64_t)16, (uint64_t)end - b);
-      const uint32_t lo = q0 > b ? (uint32_t)min((uint64_t)16, (uint64_t)q0 - b) : 0u;
-      const uint32_t in = (1u << hi) - 1u;
-      const uint32_t lf = vcf_eq16(q, '\n') & in;
-      // LF directly after byte i: bit i + 1 of lf, the quad's successor for i = 15, the window's for
-      // the window's last byte (hi < 16 only in the window's last quad)
-      uint32_t lf_after = lf >> 1;
-      if (next_lf) lf_after |= 1u << (hi - 1u);
-      const uint32_t cr = vcf_eq16(q, '\r') & in;
-      nl = (lf | (cr & ~lf_after)) & ~((1u << lo) - 1u);
-      if (want_tabs) tb = vcf_eq16(q, '\t') & in;
-    }
-    nlmap[b >> 4] = (uint16_t)nl;
-    if (want_tabs) tabmap[b >> 4] = (uint16_t)tb;
-    cnt += (uint32_t)__popc(nl);
-  }
-  const uint32_t tot = wave_last(wave_scan_dpp(cnt));
-  if (lane == 0) count[wave] = tot;
-}
 
 // Line i of `total` starts (k_vcf_starts' array): its start, the bytes readLine consumes and the
 // bytes of its content.  Only the last start can be an unterminated line; its end is the window's.
@@ -613,59 +573,20 @@ int frag_out(hbam_ctx* c, uint64_t n, FragOut* o) {
   return HBAM_OK;
 }
 
-struct FragLines {
-  const uint8_t* d;
-  uint32_t shift, total, nl, wlen, at_eof;
-  uint32_t* starts;
-  uint16_t* tabmap;
+struct FragLines : TextLines {
+  uint32_t nl, at_eof;  // nl = the usable lines of `total`
 };
 
-// structural pass + line starts.  q0 = the first window-relative position whose terminator counts;
-// explicit_first: the reader's first line starts at q0 itself.
-int frag_lines(hbam_ctx* c, const uint8_t* text, int on_device, uint64_t text_len, uint64_t q0,
-               uint32_t explicit_first, bool at_eof, bool want_tabs, FragLines* L) {
-  int rc = stage_comp(c, text, on_device, text_len, &L->d);
+// text_lines under LineReader's line rule, and the usable lines: before the end of the file the
+// last start is an incomplete line; at it, a start at the window's end is no line
+int frag_text_lines(hbam_ctx* c, const uint8_t* text, int on_device, uint64_t text_len, uint64_t q0,
+                    uint32_t explicit_first, bool at_eof, bool want_tabs, FragLines* L) {
+  int rc = text_lines(c, text, on_device, text_len, q0, explicit_first, true, at_eof, want_tabs, L);
   if (rc) return rc;
-  if (q0 >= text_len) explicit_first = 0;  // the reader opens at the window's end: no line starts there
-  const uint32_t shift = (uint32_t)((uintptr_t)L->d & 15u);
-  const uint32_t end = (uint32_t)text_len + shift;
-  const uint32_t ntiles = (end + VCF_TILE - 1) / VCF_TILE;
-  L->shift = shift;
-  L->wlen = (uint32_t)text_len;
   L->at_eof = at_eof;
-  L->tabmap = nullptr;
-  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-  uint64_t m_all = 0;
-  uint16_t* nlmap = nullptr;
-  uint64_t* tfirst = nullptr;
-  if (ntiles) {
-    uint32_t* cnt;
-    const uint64_t quads = (uint64_t)ntiles * (VCF_TILE / 16);
-    if ((rc = ensure(c, B_VCF_NL, quads, &nlmap)) || (want_tabs && (rc = ensure(c, B_VCF_TAB, quads + 4, &L->tabmap))) ||
-        (rc = ensure(c, B_VCF_CNT, (uint64_t)ntiles + 1, &cnt)) ||
-        (rc = ensure(c, B_VCF_OFF, (uint64_t)ntiles + 1, &tfirst)))
-      return rc;
-    k_seq_scan<<<grid_for(ntiles, VCF_WG / 64), VCF_WG, 0, c->stream>>>(L->d - shift, end, (uint32_t)q0 + shift, ntiles,
-                                                                         at_eof ? 0u : 1u, want_tabs ? 1u : 0u, nlmap,
-                                                                         L->tabmap, cnt);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    if ((rc = scan_exclusive<uint32_t>(c, cnt, ntiles, tfirst, &m_all))) return rc;
-  } else {
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-  }
-  const uint64_t total = m_all + explicit_first;
-  if ((rc = ensure(c, B_VCF_STARTS, total + 2, &L->starts))) return rc;
-  if (ntiles)
-    k_vcf_starts<<<grid_for(ntiles, VCF_WG / 64), VCF_WG, 0, c->stream>>>(
-        nlmap, ntiles, tfirst, shift, explicit_first, (uint32_t)q0, (uint32_t)total, (uint32_t)text_len, L->starts);
-  HIPCHK(c, hipGetLastError());
-  L->total = (uint32_t)total;
-  // the usable lines: before the end of the file the last start is an incomplete line; at it, a
-  // start at the window's end is no line
   uint32_t last = 0;
-  if (total) HIPCHK(c, copy_sync(c, &last, L->starts + (total - 1), 4, hipMemcpyDeviceToHost));
-  L->nl = total == 0 ? 0u : (at_eof ? (uint32_t)total - (last >= L->wlen ? 1u : 0u) : (uint32_t)total - 1u);
+  if (L->total) HIPCHK(c, copy_sync(c, &last, L->starts + (L->total - 1), 4, hipMemcpyDeviceToHost));
+  L->nl = L->total == 0 ? 0u : (at_eof ? L->total - (last >= L->wlen ? 1u : 0u) : L->total - 1u);
   return HBAM_OK;
 }
 
@@ -828,7 +749,7 @@ extern "C" int hbam_fastq_decode_split(hbam_ctx* c, const uint8_t* text, int on_
   const uint64_t end_abs = length > ~0ull - start ? ~0ull : start + length;
   c->timing = hbam_timing{};
   FragLines L;
-  if ((rc = frag_lines(c, text, on_device, text_len, q0, 1, at_eof, false, &L))) return rc;
+  if ((rc = frag_text_lines(c, text, on_device, text_len, q0, 1, at_eof, false, &L))) return rc;
   uint32_t r0 = 0;
   uint64_t first_pos = start;
   const uint64_t hi64 = end_abs > text_base ? end_abs - text_base : 0;
@@ -890,7 +811,7 @@ extern "C" int hbam_qseq_decode_split(hbam_ctx* c, const uint8_t* text, int on_d
   const uint64_t end_abs = length > ~0ull - start ? ~0ull : start + length;
   c->timing = hbam_timing{};
   FragLines L;
-  if ((rc = frag_lines(c, text, on_device, text_len, q0, start == 0 ? 1u : 0u, at_eof, true, &L))) return rc;
+  if ((rc = frag_text_lines(c, text, on_device, text_len, q0, start == 0 ? 1u : 0u, at_eof, true, &L))) return rc;
   uint64_t first_pos = 0;
   if (start > 0) {
     if (L.total == 0 && !at_eof) return frag_nothing(c, L, text_base, start, HBAM_EMORE, out);

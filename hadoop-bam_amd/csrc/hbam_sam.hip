@@ -1,11 +1,13 @@
 // hbam_sam.hip — SAM text on the device: SAMRecordReader (SAMRecordReader.java) over one FileSplit.
 // The lines of the split become BAM records (BAMRecordCodec.encode, what SAMRecordWritable.write
 // sends through the shuffle) packed into the context's ubuf, and the BAM path's own k_decode_fixed,
-// pool scans and k_decode_pools run over them: the result is the hbam_columns of hbam_decode_split.
-// Included at the end of hbam_capi.hip, after hbam_vcf.hip (it uses that file's structural pass,
-// line-start scatter and contig table).  gfx950, wave64.
+// pool scans and k_decode_pools run over them (finish_pools, columns_out): the result is the
+// hbam_columns of hbam_decode_split.  Included at the end of hbam_capi.hip, after hbam_lines.hip (the
+// line-structure front end and the name table's helpers) and hbam_vcf.hip (the CharSequence hash).
+// gfx950, wave64.
 //
-//   k_vcf_scan, k_vcf_starts   newline / tab bitmaps, the start of every line (hbam_vcf.hip)
+//   k_line_scan<false, true>, k_vcf_starts   newline / tab bitmaps, the start of every line
+//                      (text_lines, hbam_lines.hip)
 //   k_sam_sizes        a lane per line: the line parsed by sam_line (sam_line.h) for its record
 //                      size and status; the tabs come from the tab bitmap, the tags decide the aux
 //                      size.  SEQ and QUAL are not read (their lengths are tab positions); the other
@@ -221,98 +223,49 @@ extern "C" int hbam_sam_decode_split(hbam_ctx* c, const uint8_t* text, int on_de
   if (start != 0 && start < data_start)
     return set_err(c, HBAM_EUNSUPPORTED, "a SAM split that begins inside the header (start %llu < data_start %llu)",
                    (unsigned long long)start, (unsigned long long)data_start);
-  uint32_t used = 0;
-  for (uint32_t i = 0; i < table_size; ++i) {
-    if (table[i].ordinal < 0) continue;
-    ++used;
-    if ((uint64_t)table[i].name_off + table[i].name_len > names_len)
-      return set_err(c, HBAM_EINVAL, "dictionary table entry %u points outside the names", i);
-  }
-  if ((uint64_t)used * 2 > table_size)  // a probe ends at an empty slot
-    return set_err(c, HBAM_EINVAL, "the dictionary table must be at least twice the number of sequences");
+  int rc = contig_table_check(c, table, table_size, names_len, DICTIONARY_TABLE);
+  if (rc) return rc;
   // The split returns the lines whose first byte b has max(start, data_start) <= b < start + length
   // (SAMRecordReader.initialize and its WorkaroundingStream): a split at 0 begins at data_start, any
-  // other opens at start - 1 and discards through the first '\n'
-  const uint64_t q0_abs = start ? start - 1 : data_start;
-  if (q0_abs < text_base) return set_err(c, HBAM_EINVAL, "the window starts after the reader's first byte");
-  const uint64_t q0 = std::min(q0_abs - text_base, text_len);
+  // other opens at start - 1 and discards through the first '\n' (reader_bounds)
   const uint64_t hi_abs = std::min(start + length, file_len);
-  const uint32_t hi = (uint32_t)std::min<uint64_t>(hi_abs > text_base ? hi_abs - text_base : 0, 0xffffffffull);
-  const uint32_t explicit_first = (start == 0 && q0_abs - text_base < text_len) ? 1u : 0u;
-  const uint64_t window_end = text_base + text_len;
+  ReaderBounds b;
+  if ((rc = reader_bounds(c, start, data_start, text_base, text_len, hi_abs, &b))) return rc;
   c->timing = hbam_timing{};
-  const uint8_t* d;
-  int rc = stage_comp(c, text, on_device, text_len, &d);
-  if (rc) return rc;
-  const uint32_t shift = (uint32_t)((uintptr_t)d & 15u);
-  const uint32_t end = (uint32_t)text_len + shift;
-  const uint32_t ntiles = (end + VCF_TILE - 1) / VCF_TILE;
-  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-  uint64_t m_all = 0;
-  uint16_t *nlmap = nullptr, *tabmap = nullptr;
-  uint64_t* tfirst = nullptr;
-  if (ntiles) {
-    uint32_t* cnt;
-    const uint64_t quads = (uint64_t)ntiles * (VCF_TILE / 16);
-    if ((rc = ensure(c, B_VCF_NL, quads, &nlmap)) || (rc = ensure(c, B_VCF_TAB, quads + 4, &tabmap)) ||
-        (rc = ensure(c, B_VCF_CNT, (uint64_t)ntiles + 1, &cnt)) ||
-        (rc = ensure(c, B_VCF_OFF, (uint64_t)ntiles + 1, &tfirst)))
-      return rc;
-    k_vcf_scan<<<grid_for(ntiles, VCF_WG / 64), VCF_WG, 0, c->stream>>>(d - shift, end, (uint32_t)q0 + shift, ntiles,
-                                                                         nlmap, tabmap, cnt);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    if ((rc = scan_exclusive<uint32_t>(c, cnt, ntiles, tfirst, &m_all))) return rc;
-  } else {
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-  }
-  const uint64_t total = m_all + explicit_first;
-  uint32_t *starts, *rsize;
+  TextLines L;
+  if ((rc = text_lines(c, text, on_device, text_len, b.q0, b.explicit_first, false, false, true, &L))) return rc;
+  const uint64_t total = L.total;
+  const uint8_t* const d = L.d;
+  const uint32_t shift = L.shift;
+  uint32_t* const starts = L.starts;
+  const uint16_t* const tabmap = L.tabmap;
+  uint32_t* rsize;
   int32_t* lstatus;
   uint4* desc;
   uint64_t* small;
-  if ((rc = ensure(c, B_VCF_STARTS, total + 2, &starts)) || (rc = ensure(c, B_SAM_RSIZE, total + 1, &rsize)) ||
-      (rc = ensure(c, B_SAM_STATUS, total + 1, &lstatus)) || (rc = ensure(c, B_SAM_DESC, total + 1, &desc)) ||
-      (rc = ensure(c, B_VCF_SMALL, 4, &small)))
+  if ((rc = ensure(c, B_SAM_RSIZE, total + 1, &rsize)) || (rc = ensure(c, B_SAM_STATUS, total + 1, &lstatus)) ||
+      (rc = ensure(c, B_SAM_DESC, total + 1, &desc)) || (rc = ensure(c, B_VCF_SMALL, 4, &small)))
     return rc;
   unsigned long long* first_stop = (unsigned long long*)small;
   uint32_t* n_cand_d = (uint32_t*)(small + 1);
   HIPCHK(c, hipMemsetAsync(small, 0xff, 8, c->stream));
   HIPCHK(c, hipMemsetAsync(small + 1, 0, 8, c->stream));
-  if (ntiles)
-    k_vcf_starts<<<grid_for(ntiles, VCF_WG / 64), VCF_WG, 0, c->stream>>>(
-        nlmap, ntiles, tfirst, shift, explicit_first, (uint32_t)q0, (uint32_t)total, (uint32_t)text_len, starts);
-  HIPCHK(c, hipGetLastError());
   hbam_vcf_contig* dtab = nullptr;
   uint8_t* dnames = nullptr;
   if (total) {
-    if ((rc = ensure(c, B_VCF_TABLE, (uint64_t)table_size, &dtab)) ||
-        (rc = ensure(c, B_VCF_NAMES, names_len + 1, &dnames)))
-      return rc;
-    HIPCHK(c, hipMemcpyAsync(dtab, table, (size_t)table_size * sizeof *table, hipMemcpyHostToDevice, c->stream));
-    if (names_len) HIPCHK(c, hipMemcpyAsync(dnames, names, names_len, hipMemcpyHostToDevice, c->stream));
+    if ((rc = contig_table_upload(c, table, table_size, names, names_len, &dtab, &dnames))) return rc;
     k_sam_sizes<<<grid_for(total, SAM_WG), SAM_WG, 0, c->stream>>>(d, (const uint64_t*)tabmap, shift, starts,
-                                                                  (uint32_t)total, hi, dtab, table_size - 1, dnames,
+                                                                  (uint32_t)total, b.hi, dtab, table_size - 1, dnames,
                                                                   rsize, lstatus, first_stop, n_cand_d);
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, hipMemcpyAsync(c->pinned_small + 8, small, 16, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t fs = c->pinned_small[8];
-  const uint64_t n_cand = c->pinned_small[9] & 0xffffffffull;
-  uint64_t n = n_cand;
-  int32_t status = HBAM_OK;
-  // the window ends inside the last line it would return (or before the split's bound with no line
-  // at all), and the file goes on: the caller passes a longer window
-  const bool cut = window_end < file_len &&
-                   (total == 0 ? window_end < hi_abs : (n_cand == total && fs >= total - 1));
-  if (cut) {
-    n = total ? total - 1 : 0;
-    status = HBAM_EMORE;
-  } else if (fs < n_cand) {
-    n = fs;
-    HIPCHK(c, copy_sync(c, &status, lstatus + fs, 4, hipMemcpyDeviceToHost));
-  }
+  uint64_t n;
+  int32_t status;
+  if ((rc = window_cut(c, c->pinned_small[8], c->pinned_small[9] & 0xffffffffull, total, text_base + text_len, file_len,
+                       hi_abs, lstatus, &n, &status)))
+    return rc;
   // record offsets, the records, SEQ and QUAL
   uint64_t *rec_off, *voff;
   uint64_t utotal = 0;
@@ -356,73 +309,9 @@ extern "C" int hbam_sam_decode_split(hbam_ctx* c, const uint8_t* text, int on_de
   }
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
-  uint64_t tot_name = 0, tot_cig = 0, tot_seq = 0, tot_aux = 0;
-  {
-    const uint32_t tiles = (uint32_t)std::max<uint64_t>(1, (n + SCAN4_TILE - 1) / SCAN4_TILE);
-    uint64_t* partial;
-    if ((rc = ensure(c, B_PARTIAL, 4ull * tiles + 1, &partial))) return rc;
-    const Scan4In in{{dc.name_len, dc.cigar_n, dc.seq_len, dc.aux_len}};
-    const Scan4Out so{{dc.name_off, dc.cigar_off, dc.seq_off, dc.aux_off}};
-    k_scan4_reduce<<<tiles, 256, 0, c->stream>>>(in, n, partial, tiles);
-    k_scan4_partials<<<4, 256, 0, c->stream>>>(partial, tiles, so, n);
-    k_scan4_apply<<<tiles, 256, 0, c->stream>>>(in, n, partial, tiles, so);
-    HIPCHK(c, hipGetLastError());
-    const uint64_t* offs[4] = {dc.name_off, dc.cigar_off, dc.seq_off, dc.aux_off};
-    for (int q = 0; q < 4; ++q)
-      HIPCHK(c, hipMemcpyAsync(c->pinned_small + 96 + q, offs[q] + n, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->pinned_small + 8, small, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    tot_name = c->pinned_small[96];
-    tot_cig = c->pinned_small[97];
-    tot_seq = c->pinned_small[98];
-    tot_aux = c->pinned_small[99];
-  }
-  if (c->pinned_small[8] < n)  // k_decode_fixed stops at no record the encoder wrote
-    return set_err(c, HBAM_EDEVICE, "hbam_sam_decode_split: record %llu does not decode",
-                   (unsigned long long)c->pinned_small[8]);
-  if ((rc = ensure(c, B_C_NAMES, tot_name + 1, &dc.names))) return rc;
-  if ((rc = ensure(c, B_C_CIGARS, tot_cig + 1, &dc.cigars))) return rc;
-  if ((rc = ensure(c, B_C_SEQ, tot_seq + 1, &dc.seq))) return rc;
-  if ((rc = ensure(c, B_C_QUAL, tot_seq + 1, &dc.qual))) return rc;
-  if ((rc = ensure(c, B_C_AUX, tot_aux + 1, &dc.aux))) return rc;
-  HIPCHK(c, hipEventRecord(c->ev[7], c->stream));
-  if (n)
-    k_decode_pools<<<(uint32_t)std::min<uint64_t>(grid_for(n, 256), POOLS_MAX_WG), 256, 0, c->stream>>>(ub, n, rec_off,
-                                                                                                       dc);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(c->ev[8], c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-
-  out->n_records = n;
-  out->status = status;
-  out->err_record = status ? n : 0;
-  out->voffset = voff;
-  out->key = dc.key;
-  out->rec_off = rec_off;
-  out->ubuf = ub;
-  out->ubuf_len = utotal;
-  out->block_size = dc.block_size;
-  out->ref_id = dc.ref_id;
-  out->pos = dc.pos;
-  out->l_read_name = dc.l_read_name;
-  out->mapq = dc.mapq;
-  out->bin = dc.bin;
-  out->n_cigar = dc.n_cigar;
-  out->flag = dc.flag;
-  out->l_seq = dc.l_seq;
-  out->next_ref_id = dc.next_ref_id;
-  out->next_pos = dc.next_pos;
-  out->tlen = dc.tlen;
-  out->layout_ok = dc.layout_ok;
-  out->name_off = dc.name_off;
-  out->names = dc.names;
-  out->cigar_off = dc.cigar_off;
-  out->cigars = dc.cigars;
-  out->seq_off = dc.seq_off;
-  out->seq = dc.seq;
-  out->qual = dc.qual;
-  out->aux_off = dc.aux_off;
-  out->aux = dc.aux;
+  // (small: k_decode_fixed's first stop comes back with the pool totals)
+  if ((rc = finish_pools(c, ub, n, rec_off, dc, small))) return rc;
+  columns_out(out, dc, voff, rec_off, ub, utotal, n, status, status ? n : 0);
 
   c->timing.scan_ms = ev_ms(c, 0, 1);
   c->timing.walk_ms = ev_ms(c, 1, 2);
@@ -430,11 +319,9 @@ extern "C" int hbam_sam_decode_split(hbam_ctx* c, const uint8_t* text, int on_de
   c->timing.huffman_ms = ev_ms(c, 2, 11);  // of the encode: the per-line pass ...
   c->timing.resolve_ms = ev_ms(c, 11, 3);  // ... and SEQ / QUAL
   c->timing.decode_ms = ev_ms(c, 5, 6);
-  c->timing.pools_ms = ev_ms(c, 7, 8);
   c->timing.total_ms = ev_ms(c, 0, 8);
   c->timing.comp_bytes = text_len;
   c->timing.ubuf_bytes = utotal;
   c->timing.n_records = n;
-  c->timing.pool_bytes = tot_name + 4 * tot_cig + 2 * tot_seq + tot_aux;
   return HBAM_OK;
 }

@@ -1,13 +1,10 @@
 // hbam_vcf.hip — text VCF on the device: VCFRecordReader (VCFRecordReader.java:72-142) over one
 // FileSplit, and the line gather of the vcf-sort plugin (cli/plugins/VCFSort.java).  Included at
-// the end of hbam_capi.hip (it uses that file's buffers, scan and staging helpers).  gfx950, wave64.
+// the end of hbam_capi.hip, after hbam_lines.hip (it uses that file's buffers, scan and staging
+// helpers, and the shared line-structure front end).  gfx950, wave64.
 //
-//   k_vcf_scan          structural pass: every lane loads 16 bytes (a wave covers 1 KiB per step,
-//                       a tile is VCF_STEPS steps), turns them into a 16-bit '\n' mask and a 16-bit
-//                       '\t' mask, stores both bitmaps and the tile's '\n' count.
-//   (scan_exclusive)    line counts per tile -> first line index of each tile.
-//   k_vcf_starts        scatter: the start offset of every line (the byte after each '\n') from the
-//                       '\n' bitmap alone (1/8 of the text's bytes).
+//   k_line_scan<false, true>, (scan_exclusive), k_vcf_starts   the '\n' and '\t' bitmaps and the
+//                       start offset of every line: text_lines (hbam_lines.hip).
 //   k_vcf_fields        field pass, a lane per line: the first 8 tabs from the tab bitmap, the line
 //                       length ('\r' before the '\n' trimmed), POS, len(REF), CHROM -> contig
 //                       ordinal (open-addressing table, byte compare) or the CharSequence
@@ -24,11 +21,6 @@
 
 namespace hbam {
 
-constexpr uint32_t VCF_WG = 256;
-constexpr uint32_t VCF_STEPS = 4;                 // 1 KiB wave steps per tile
-constexpr uint32_t VCF_TILE = 1024 * VCF_STEPS;   // bytes per wave
-constexpr uint64_t VCF_MAX_WINDOW = 1ull << 31;   // relative offsets are u32
-
 struct VcfCols {
   uint64_t* line_off;
   int64_t* key;
@@ -39,77 +31,6 @@ struct VcfCols {
   int32_t* ref_len;
   int32_t* status;
 };
-
-// bit j = (byte j of the 16 == c)
-__device__ __forceinline__ uint32_t vcf_eq4(uint32_t w, uint32_t c4) {
-  const uint32_t x = w ^ c4;
-  const uint32_t t = ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);  // 0x80 in every zero byte
-  return (((t >> 7) * 0x00204081u) >> 21) & 0xfu;
-}
-__device__ __forceinline__ uint32_t vcf_eq16(const uint4 q, uint32_t c) {
-  const uint32_t c4 = c * 0x01010101u;
-  return vcf_eq4(q.x, c4) | vcf_eq4(q.y, c4) << 4 | vcf_eq4(q.z, c4) << 8 | vcf_eq4(q.w, c4) << 12;
-}
-
-// Positions in the three structural kernels are `shifted`: relative to text16 = the window's first
-// byte rounded down to 16 (shift = the bytes in between), so every load is an aligned quad.
-// end = window bytes + shift; q0 = the first position whose '\n' starts a line of this reader.
-__global__ __launch_bounds__(VCF_WG) void k_vcf_scan(const uint8_t* __restrict__ text16, uint32_t end, uint32_t q0,
-                                                     uint32_t ntiles, uint16_t* __restrict__ nlmap,
-                                                     uint16_t* __restrict__ tabmap, uint32_t* __restrict__ count) {
-  const uint32_t wave = blockIdx.x * (VCF_WG / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-  if (wave >= ntiles) return;  // wave-uniform
-  uint32_t cnt = 0;
-#pragma unroll
-  for (uint32_t s = 0; s < VCF_STEPS; ++s) {
-    const uint64_t b = (uint64_t)wave * VCF_TILE + s * 1024u + lane * 16u;
-    uint32_t nl = 0, tb = 0;
-    if (b < end) {
-      const uint4 q = *reinterpret_cast<const uint4*>(text16 + b);
-      const uint32_t hi = (uint32_t)min((uint64_t)16, (uint64_t)end - b);
-      const uint32_t lo = q0 > b ? (uint32_t)min((uint64_t)16, (uint64_t)q0 - b) : 0u;
-      const uint32_t in = (1u << hi) - 1u;
-      tb = vcf_eq16(q, '\t') & in;
-      nl = vcf_eq16(q, '\n') & in & ~((1u << lo) - 1u);
-    }
-    nlmap[b >> 4] = (uint16_t)nl;
-    tabmap[b >> 4] = (uint16_t)tb;
-    cnt += (uint32_t)__popc(nl);
-  }
-  const uint32_t tot = wave_last(wave_scan_dpp(cnt));
-  if (lane == 0) count[wave] = tot;
-}
-
-// starts[first + k] = the byte after the k-th counted '\n' (window-relative, unshifted);
-// starts[0] = first_start when the reader has a first line that no '\n' of the window precedes
-// (explicit = 1: a split starting at 0 begins at data_start); starts[total] = wlen + 1, so the
-// last line's end (starts[i + 1] - 1) is the end of the window.
-__global__ __launch_bounds__(VCF_WG) void k_vcf_starts(const uint16_t* __restrict__ nlmap, uint32_t ntiles,
-                                                       const uint64_t* __restrict__ tile_first, uint32_t shift,
-                                                       uint32_t explicit_first, uint32_t first_start, uint32_t total,
-                                                       uint32_t wlen, uint32_t* __restrict__ starts) {
-  const uint32_t wave = blockIdx.x * (VCF_WG / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-  if (wave >= ntiles) return;
-  if (wave == 0 && lane == 0) {
-    if (explicit_first) starts[0] = first_start;
-    starts[total] = wlen + 1u;
-  }
-  uint32_t base = (uint32_t)tile_first[wave] + explicit_first;
-  for (uint32_t s = 0; s < VCF_STEPS; ++s) {
-    const uint64_t b = (uint64_t)wave * VCF_TILE + s * 1024u + lane * 16u;
-    uint32_t m = nlmap[b >> 4];
-    const uint32_t c = (uint32_t)__popc(m);
-    const uint32_t incl = wave_scan_dpp(c);
-    uint32_t at = base + incl - c;
-    while (m) {
-      const uint32_t j = (uint32_t)__builtin_ctz(m);
-      m &= m - 1u;
-      if (at < total) starts[at] = (uint32_t)b + j + 1u - shift;  // (at < total always: a bound, not a rule)
-      ++at;
-    }
-    base += wave_last(incl);
-  }
-}
 
 __device__ __forceinline__ uint64_t vcf_rotl(uint64_t x, int r) { return x << r | x >> (64 - r); }
 __device__ __forceinline__ uint64_t vcf_fmix(uint64_t k) {
@@ -318,100 +239,44 @@ extern "C" int hbam_vcf_decode_split(hbam_ctx* c, const uint8_t* text, int on_de
     return set_err(c, HBAM_EINVAL, "the contig table's size must be a power of two");
   if (text_len > VCF_MAX_WINDOW) return set_err(c, HBAM_EINVAL, "a VCF window is at most 2 GiB");
   if (text_base + text_len > file_len) return set_err(c, HBAM_EINVAL, "window past the end of the file");
-  uint32_t used = 0;
-  for (uint32_t i = 0; i < table_size; ++i) {
-    if (table[i].ordinal < 0) continue;
-    ++used;
-    if ((uint64_t)table[i].name_off + table[i].name_len > names_len)
-      return set_err(c, HBAM_EINVAL, "contig table entry %u points outside the names", i);
-  }
-  if ((uint64_t)used * 2 > table_size)  // a probe ends at an empty slot
-    return set_err(c, HBAM_EINVAL, "the contig table must be at least twice the number of contigs");
-  // the reader is opened at q0: a split at 0 reads from data_start, any other discards through the
-  // first '\n' at or after start - 1 (VCFRecordReader.java:101-117)
-  const uint64_t q0_abs = start ? start - 1 : data_start;
-  if (q0_abs < text_base) return set_err(c, HBAM_EINVAL, "the window starts after the reader's first byte");
-  const uint64_t q0 = std::min(q0_abs - text_base, text_len);
-  // nextKeyValue: a line is returned while one exists and its position < length (:129), positions
-  // counted from where the reader was opened (0, or start - 1)
-  const uint64_t hi_abs = std::min(start ? start + length - 1 : length, file_len);
-  const uint32_t hi = (uint32_t)std::min<uint64_t>(hi_abs > text_base ? hi_abs - text_base : 0, 0xffffffffull);
-  const uint32_t explicit_first = (start == 0 && q0_abs - text_base < text_len) ? 1u : 0u;
-  const uint64_t window_end = text_base + text_len;
-  c->timing = hbam_timing{};
-  const uint8_t* d;
-  int rc = stage_comp(c, text, on_device, text_len, &d);
+  int rc = contig_table_check(c, table, table_size, names_len, CONTIG_TABLE);
   if (rc) return rc;
-  const uint32_t shift = (uint32_t)((uintptr_t)d & 15u);
-  const uint32_t end = (uint32_t)text_len + shift;
-  const uint32_t ntiles = (end + VCF_TILE - 1) / VCF_TILE;
-  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-  uint64_t m_all = 0;
-  uint16_t *nlmap = nullptr, *tabmap = nullptr;
-  uint64_t* tfirst = nullptr;
-  if (ntiles) {
-    uint32_t* cnt;
-    const uint64_t quads = (uint64_t)ntiles * (VCF_TILE / 16);
-    // + 4: the field pass reads the 64-bit tab word of a line that starts at the window's last byte + 1
-    if ((rc = ensure(c, B_VCF_NL, quads, &nlmap)) || (rc = ensure(c, B_VCF_TAB, quads + 4, &tabmap)) ||
-        (rc = ensure(c, B_VCF_CNT, (uint64_t)ntiles + 1, &cnt)) ||
-        (rc = ensure(c, B_VCF_OFF, (uint64_t)ntiles + 1, &tfirst)))
-      return rc;
-    k_vcf_scan<<<grid_for(ntiles, VCF_WG / 64), VCF_WG, 0, c->stream>>>(d - shift, end, (uint32_t)q0 + shift, ntiles,
-                                                                         nlmap, tabmap, cnt);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    if ((rc = scan_exclusive<uint32_t>(c, cnt, ntiles, tfirst, &m_all))) return rc;
-  } else {
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-  }
-  const uint64_t total = m_all + explicit_first;
+  // VCFRecordReader.java:101-117 opens the reader (reader_bounds).  nextKeyValue: a line is returned
+  // while one exists and its position < length (:129), positions counted from where the reader was
+  // opened (0, or start - 1)
+  const uint64_t hi_abs = std::min(start ? start + length - 1 : length, file_len);
+  ReaderBounds b;
+  if ((rc = reader_bounds(c, start, data_start, text_base, text_len, hi_abs, &b))) return rc;
+  c->timing = hbam_timing{};
+  TextLines L;
+  if ((rc = text_lines(c, text, on_device, text_len, b.q0, b.explicit_first, false, false, true, &L))) return rc;
+  const uint64_t total = L.total;
+  const uint8_t* const d = L.d;
   VcfCols vc;
-  uint32_t* starts;
   uint64_t* small;
-  if ((rc = vcf_cols(c, total, &vc)) || (rc = ensure(c, B_VCF_STARTS, total + 2, &starts)) ||
-      (rc = ensure(c, B_VCF_SMALL, 4, &small)))
-    return rc;
+  if ((rc = vcf_cols(c, total, &vc)) || (rc = ensure(c, B_VCF_SMALL, 4, &small))) return rc;
   unsigned long long* first_stop = (unsigned long long*)small;
   uint32_t* n_cand_d = (uint32_t*)(small + 1);
   HIPCHK(c, hipMemsetAsync(small, 0xff, 8, c->stream));
   HIPCHK(c, hipMemsetAsync(small + 1, 0, 8, c->stream));
-  if (ntiles)
-    k_vcf_starts<<<grid_for(ntiles, VCF_WG / 64), VCF_WG, 0, c->stream>>>(
-        nlmap, ntiles, tfirst, shift, explicit_first, (uint32_t)q0, (uint32_t)total, (uint32_t)text_len, starts);
-  HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
   if (total) {
     hbam_vcf_contig* dtab;
     uint8_t* dnames;
-    if ((rc = ensure(c, B_VCF_TABLE, (uint64_t)table_size, &dtab)) ||
-        (rc = ensure(c, B_VCF_NAMES, names_len + 1, &dnames)))
-      return rc;
-    HIPCHK(c, hipMemcpyAsync(dtab, table, (size_t)table_size * sizeof *table, hipMemcpyHostToDevice, c->stream));
-    if (names_len) HIPCHK(c, hipMemcpyAsync(dnames, names, names_len, hipMemcpyHostToDevice, c->stream));
-    k_vcf_fields<<<grid_for(total, VCF_WG), VCF_WG, 0, c->stream>>>(d, (const uint64_t*)tabmap, shift, starts,
-                                                                    (uint32_t)total, hi, text_base, dtab,
+    if ((rc = contig_table_upload(c, table, table_size, names, names_len, &dtab, &dnames))) return rc;
+    k_vcf_fields<<<grid_for(total, VCF_WG), VCF_WG, 0, c->stream>>>(d, (const uint64_t*)L.tabmap, L.shift, L.starts,
+                                                                    (uint32_t)total, b.hi, text_base, dtab,
                                                                     table_size - 1, dnames, vc, first_stop, n_cand_d);
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
   HIPCHK(c, hipMemcpyAsync(c->pinned_small, small, 16, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t fs = c->pinned_small[0];
-  const uint64_t n_cand = c->pinned_small[1] & 0xffffffffull;
-  uint64_t n = n_cand;
-  int32_t status = HBAM_OK;
-  // the window ends inside the last line it would return (or before the reader's bound with no line
-  // at all), and the file goes on: the caller passes a longer window
-  const bool cut = window_end < file_len &&
-                   (total == 0 ? window_end < hi_abs : (n_cand == total && fs >= total - 1));
-  if (cut) {
-    n = total ? total - 1 : 0;
-    status = HBAM_EMORE;
-  } else if (fs < n_cand) {
-    n = fs;
-    HIPCHK(c, copy_sync(c, &status, vc.status + fs, 4, hipMemcpyDeviceToHost));
-  }
+  uint64_t n;
+  int32_t status;
+  if ((rc = window_cut(c, c->pinned_small[0], c->pinned_small[1] & 0xffffffffull, total, text_base + text_len, file_len,
+                       hi_abs, vc.status, &n, &status)))
+    return rc;
   out->n = n;
   out->status = status;
   out->line_off = vc.line_off;

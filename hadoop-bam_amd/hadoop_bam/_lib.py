@@ -378,6 +378,14 @@ def host_columns_to_numpy(h):
     return out
 
 
+def _host_array(ptr, count, dt):
+    """A copy of `count` elements of dtype `dt` at a host pointer of any ctypes pointer type."""
+    if not count:
+        return np.zeros(0, dt)
+    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)),
+                                 shape=(count * np.dtype(dt).itemsize,)).view(dt).copy()
+
+
 class Context:
     """One device context (hbam_ctx): a HIP stream plus device work buffers."""
 
@@ -1021,15 +1029,9 @@ class Context:
             return {"rc": rc, "error": self.last_error()}
         k = int(h.n)
         out = {"rc": 0, "n": k, "status": int(h.status)}
-
-        def arr(ptr, count, dt):
-            if not count:
-                return np.zeros(0, dt)
-            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)),
-                                         shape=(count * np.dtype(dt).itemsize,)).view(dt).copy()
         for name, dt in VCF_FIELDS:
-            out[name] = arr(getattr(h, name), k, dt)
-        out["tab"] = arr(h.tab, 8 * k, np.uint32).reshape(k, 8)
+            out[name] = _host_array(getattr(h, name), k, dt)
+        out["tab"] = _host_array(h.tab, 8 * k, np.uint32).reshape(k, 8)
         self.L.hbam_vcf_release(self.h, C.byref(h))
         out["timing"] = self.timing()
         return out
@@ -1065,19 +1067,13 @@ class Context:
         k = int(h.n)
         out = {"rc": 0, "n": k, "status": int(h.status), "err_pos": int(h.err_pos), "first_pos": int(h.first_pos),
                "end_pos": int(h.end_pos)}
-
-        def arr(ptr, count, dt):
-            if not count:
-                return np.zeros(0, dt)
-            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)),
-                                         shape=(count * np.dtype(dt).itemsize,)).view(dt).copy()
         for name, dt in FRAG_FIELDS:
-            out[name] = arr(getattr(h, name), k, dt)
+            out[name] = _host_array(getattr(h, name), k, dt)
         for name in ("instrument", "flowcell", "index"):
-            out[name] = arr(getattr(h, name), 2 * k, np.uint32).reshape(k, 2)
+            out[name] = _host_array(getattr(h, name), 2 * k, np.uint32).reshape(k, 2)
         for name in ("key", "seq", "qual"):
-            out[name + "_off"] = arr(getattr(h, name + "_off"), k + 1, np.uint64)
-            out[name] = arr(getattr(h, name), int(getattr(h, name + "_len")), np.uint8)
+            out[name + "_off"] = _host_array(getattr(h, name + "_off"), k + 1, np.uint64)
+            out[name] = _host_array(getattr(h, name), int(getattr(h, name + "_len")), np.uint8)
         self.L.hbam_frag_release(self.h, C.byref(h))
         out["timing"] = self.timing()
         return out

@@ -20,6 +20,7 @@ import zlib
 import numpy as np
 
 from . import _lib
+from ._window import read_growing_window
 from .formats import (FileSplit, FormatException, IllegalArgumentException,  # noqa: F401
                       NumberFormatException, SeekableFile, context, raise_for)
 
@@ -189,18 +190,16 @@ def read_split_columns(ctx, fmt, ss, start, length, encoding, filter_failed_qc):
     reader's first byte (start for FASTQ, start - 1 for QSEQ) to start + length + tail, the tail
     growing x4 from SEQ_WINDOW_TAIL while the call answers HBAM_EMORE (length None: the whole file)
     -> (host columns, window base, window)."""
-    base = min(start if fmt == "fastq" else max(start - 1, 0), ss.length)
-    tail = SEQ_WINDOW_TAIL
-    while True:
-        stop = ss.length if length is None else max(base, min(ss.length, start + length + tail))
-        window = ss.read_at(base, stop - base)
+    def call(window, base):
         cols = ctx.frag_decode_split(fmt, window, start, length, encoding, filter_failed_qc, text_base=base,
                                      file_len=ss.length)
         if cols["rc"]:
             raise_for(cols["rc"], cols.get("error", ""))
-        if cols["status"] != _lib.HBAM_EMORE or stop == ss.length:
-            return cols, base, window
-        tail *= 4
+        return cols
+
+    base = min(start if fmt == "fastq" else max(start - 1, 0), ss.length)
+    cols, window = read_growing_window(ss, base, start, length, SEQ_WINDOW_TAIL, call)
+    return cols, base, window
 
 
 class _SeqRecordReader:

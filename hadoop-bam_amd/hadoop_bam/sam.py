@@ -13,6 +13,7 @@ import os
 import numpy as np
 
 from . import _lib
+from ._window import read_growing_window
 from .formats import (BAMRecordBytes, FileSplit, IOException, LongWritable, SAMFormatException,  # noqa: F401
                       SAMRecordWritable, SeekableFile, compute_file_splits, context, raise_for)
 from .output import SAMFileHeader
@@ -110,18 +111,16 @@ def read_split_columns(ctx, ss, start, length, data_start, table, n_ref):
     """hbam_sam_decode_split over the window of FileSplit [start, start + length): file bytes
     [start - 1 (data_start for a split at 0), start + length + tail), the tail growing from
     SAM_WINDOW_TAIL while the decode answers HBAM_EMORE -> (host columns, window base, window bytes)."""
-    base = min(start - 1 if start else data_start, ss.length)
-    tail = SAM_WINDOW_TAIL
-    while True:
-        stop = max(base, min(ss.length, start + length + tail))
-        window = ss.read_at(base, stop - base)
+    def call(window, base):
         cols = ctx.sam_decode_split(window, start, length, data_start, table, n_ref, text_base=base,
                                     file_len=ss.length)
         if cols["rc"]:
             _raise(cols["rc"], cols.get("error", ""))
-        if cols["status"] != _lib.HBAM_EMORE or stop == ss.length:
-            return cols, base, len(window)
-        tail *= 4
+        return cols
+
+    base = min(start - 1 if start else data_start, ss.length)
+    cols, window = read_growing_window(ss, base, start, length, SAM_WINDOW_TAIL, call)
+    return cols, base, len(window)
 
 
 class SAMRecordReader:

@@ -17,6 +17,7 @@ from fractions import Fraction
 import numpy as np
 
 from . import _lib
+from ._window import read_growing_window
 from .formats import Configuration, IllegalArgumentException, IOException, SAMFormatException, context, raise_for
 from .output import KeyIgnoringBAMRecordWriter, read_sam_header
 from .sam import SAMFormat, read_sam_text_header
@@ -465,17 +466,16 @@ def _view_sam(ctx, path, header, data_start, w):
         start = 0
         while start < ss.length:
             length = min(ss.length - start, max(VIEW_SPLIT_BYTES, data_start + 1 - start))
-            base = min(start - 1 if start else data_start, ss.length)
-            tail = SAM_WINDOW_TAIL
-            while True:  # the window policy of sam.read_split_columns, the columns left on the device
-                stop = max(base, min(ss.length, start + length + tail))
-                rc, d = ctx.sam_decode_split_device(ss.read_at(base, stop - base), start, length, data_start, table,
-                                                    len(names), text_base=base, file_len=ss.length)
+
+            def call(window, base):  # the columns left on the device
+                rc, d = ctx.sam_decode_split_device(window, start, length, data_start, table, len(names),
+                                                    text_base=base, file_len=ss.length)
                 if rc:
                     raise_for(rc, ctx.last_error())
-                if int(d.status) != _lib.HBAM_EMORE or stop == ss.length:
-                    break
-                tail *= 4
+                return d
+
+            base = min(start - 1 if start else data_start, ss.length)
+            d, _ = read_growing_window(ss, base, start, length, SAM_WINDOW_TAIL, call)
             w.write_device(d.ubuf, d.rec_off, int(d.n_records))
             if int(d.status) != _lib.HBAM_OK:  # HBAM_EMORE with the whole rest of the file in the window too
                 raise_for(int(d.status), "line %d of the split at %d" % (int(d.n_records), start))

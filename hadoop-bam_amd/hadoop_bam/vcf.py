@@ -13,7 +13,7 @@ import os
 
 import numpy as np
 
-from . import _lib
+from ._window import read_growing_window
 from .bcf import BCFDecodeRuntimeException, TribbleException  # noqa: F401  (the reader's exceptions)
 from .bcf import _raise
 from .formats import FileSplit, IOException, SeekableFile, context, raise_for  # noqa: F401  (FileSplit: the reader's split)
@@ -164,18 +164,16 @@ def read_split_columns(ctx, ss, start, length, data_start, table):
     """hbam_vcf_decode_split over the window of FileSplit [start, start + length): file bytes
     [start - 1 (data_start for a split at 0), start + length + tail), the tail growing from
     VCF_WINDOW_TAIL while the decode answers HBAM_EMORE -> (host columns, window base, window)."""
-    base = min(start - 1 if start else data_start, ss.length)
-    tail = VCF_WINDOW_TAIL
-    while True:
-        stop = max(base, min(ss.length, start + length + tail))
-        window = ss.read_at(base, stop - base)
+    def call(window, base):
         cols = ctx.vcf_decode_split(window, start, length, data_start, table, text_base=base,
                                     file_len=ss.length)
         if cols["rc"]:
             raise_for(cols["rc"], cols.get("error", ""))
-        if cols["status"] != _lib.HBAM_EMORE or stop == ss.length:
-            return cols, base, window
-        tail *= 4
+        return cols
+
+    base = min(start - 1 if start else data_start, ss.length)
+    cols, window = read_growing_window(ss, base, start, length, VCF_WINDOW_TAIL, call)
+    return cols, base, window
 
 
 class VCFRecordReader:

@@ -101,6 +101,30 @@ def test_golden_bam_rendered_as_sam(gpu_ctx, oracle_mod, name):
     assert got["timing"]["ubuf_bytes"] == len(s.whole["ubuf"])
 
 
+def _pool_bytes(cols):
+    tot = {k: int(cols[k + "_off"][cols["n"]]) for k in ("name", "cigar", "seq", "aux")}
+    return tot["name"] + 4 * tot["cigar"] + 2 * tot["seq"] + tot["aux"]
+
+
+def test_timing_of_the_shared_record_tail(gpu_ctx, oracle_mod):
+    """The BAM decode and the SAM decode end in one record tail: each call's timing keeps its own
+    fields, and pool_bytes is the sum over the offsets that call returned."""
+    bam = np.fromfile(os.path.join(GOLDEN, "small_pe.bam"), np.uint8)
+    h = oracle_mod.read_header(bam)
+    got = gpu_ctx.decode_split(bam, h["first_voffset"], (len(bam) << 16) | 0xffff, n_ref=h["n_ref"])
+    assert got["rc"] == 0 and got["n"] > 0
+    assert got["timing"]["pool_bytes"] == _pool_bytes(got) > 0
+    assert got["timing"]["pools_ms"] > 0 and got["timing"]["n_records"] == got["n"]
+    s = Sam(sam_cases.sam_of_bam(bam)[0])
+    sam = s.decode(gpu_ctx, 0, len(s.data))
+    assert sam["n"] == got["n"]
+    t = sam["timing"]
+    assert {k for k, v in t.items() if v} == {"scan_ms", "walk_ms", "inflate_ms", "huffman_ms", "resolve_ms", "decode_ms",
+                                              "pools_ms", "total_ms", "comp_bytes", "ubuf_bytes", "n_records",
+                                              "pool_bytes"}, t
+    assert t["pool_bytes"] == _pool_bytes(sam) > 0 and t["n_records"] == sam["n"]
+
+
 @pytest.mark.parametrize("variant", ["lf", "crlf"])
 @pytest.mark.parametrize("size", [4096, 65537, 0])
 def test_generated_file_in_splits(gpu_ctx, oracle_mod, generated, variant, size):

@@ -210,6 +210,34 @@ def test_terminators_across_quad_step_and_tile(gpu_ctx, t_at, term):
                 ref_run("qseq", data, 7, len(data)), "qseq")
 
 
+def crafted_qseq(t_at, term):
+    """Four 11-field lines; the first line's terminator `term` begins at file offset t_at."""
+    rest = b"\t" + b"\t".join(QS[1:])
+    return (b"M" * (t_at - len(rest)) + rest + term + qline(f8=b"AC.T") + b"\r" + qline(f6=b"ACG") + b"\r\n"
+            + qline(f10=b"0") + b"\n")
+
+
+QS_BOUNDARIES = (31, 1023, 4095)  # (a valid line is longer than 15 bytes: the second quad's last byte)
+QS_PLACEMENTS = [(p - len(t) + 1, t) for p in QS_BOUNDARIES for t in (b"\r", b"\r\n", b"\n")]
+QS_PLACEMENTS += [(p, b"\r\n") for p in QS_BOUNDARIES]
+QS_PLACEMENTS += [(p + 1, t) for p in QS_BOUNDARIES for t in (b"\r", b"\n")]
+
+
+@pytest.mark.parametrize("t_at,term", QS_PLACEMENTS, ids=["%d-%s" % (a, t.hex()) for a, t in QS_PLACEMENTS])
+def test_qseq_terminators_across_quad_step_and_tile(gpu_ctx, t_at, term):
+    """The same placements under the structural pass that also writes the tab bitmap: the lines are
+    records here, so their fields (cut at the bitmap's tabs) are compared, not only a status."""
+    data = crafted_qseq(t_at, term)
+    want = ref_run("qseq", data, 0, len(data))
+    assert want["status"] == ref.OK and want["n"] == 4
+    assert_same(device_run(gpu_ctx, "qseq", data, 0, len(data)), want, "whole")
+    for start in (7, 13):
+        want = ref_run("qseq", data, start, len(data))
+        assert want["n"] == 3
+        assert_same(device_run(gpu_ctx, "qseq", data, start, len(data)), want, ("host", start))
+        assert_same(device_run(gpu_ctx, "qseq", data, start, len(data), device_window=True), want, ("device", start))
+
+
 @pytest.mark.parametrize("tail", [b"", b"\n", b"\r", b"\r\n", b"\r\r", b"\n\n"], ids=lambda t: t.hex() or "none")
 def test_terminator_at_the_files_last_byte(gpu_ctx, tail):
     """The end of the file counts as "not LF": a last CR ends its line; a blank line behind the last
