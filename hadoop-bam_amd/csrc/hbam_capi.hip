@@ -237,6 +237,18 @@ enum BufId {
   B_FQ_KEY,
   B_FQ_SEQ,
   B_FQ_QUAL,
+  // FASTQ / QSEQ output (hbam_fragtext.hip)
+  B_FT_COLS,
+  B_FT_KEY,
+  B_FT_SEQ,
+  B_FT_QUAL,
+  B_FT_WINDOW,
+  B_FT_LEN,
+  B_FT_BAD,
+  B_FT_DESC,
+  B_FT_LINEOFF,
+  B_FT_SMALL,
+  B_FT_TEXT,
   B_COUNT_ALL
 };
 
@@ -2723,3 +2735,4 @@ extern "C" int64_t hbam_bgzf_compress(hbam_ctx* c, const uint8_t* src, int src_o
 #include "hbam_sam.hip"
 #include "hbam_samtext.hip"
 #include "hbam_fastq.hip"
+#include "hbam_fragtext.hip"

@@ -4,7 +4,8 @@ Mirrors org.seqdoop.hadoop_bam.{BAMInputFormat, BAMRecordReader, FileVirtualSpli
 SAMRecordWritable, BAMSplitGuesser, util.BGZFSplitGuesser, util.BGZFBlockIndexer/BGZFBlockIndex/BGZFSplitFileInputFormat, SplittingBAMIndex, SplittingBAMIndexer}, the Sort plugin's
 shuffle sort (cli/plugins/Sort) and its BAM output (BAMRecordWriter, KeyIgnoringBAMOutputFormat,
 util.SAMOutputPreparer, cli.Utils.mergeSAMInto) and its SAM text output (SAMRecordWriter,
-KeyIgnoringAnySAMOutputFormat, the View plugin); compute runs
+KeyIgnoringAnySAMOutputFormat, the View plugin), and the read formats FASTQ and QSEQ in both
+directions (FastqInputFormat, QseqInputFormat, FastqOutputFormat, QseqOutputFormat); compute runs
 in libhbam.so (HIP, gfx950) through the C ABI of include/hbam.h.
 """
 from ._lib import Context, HbamUnavailable, load  # noqa: F401
@@ -25,3 +26,5 @@ from .sam_text import (  # noqa: F401
 from .fastq import (  # noqa: F401
     FastqInputFormat, FastqRecordReader, FormatConstants, FormatException, NumberFormatException,
     QseqInputFormat, QseqRecordReader, SequencedFragment)
+from .fastq_text import (  # noqa: F401
+    FastqOutputFormat, FastqRecordWriter, QseqOutputFormat, QseqRecordWriter, convert)

@@ -69,6 +69,7 @@ EXPORTS = [
     "hbam_vcf_decode_split", "hbam_vcf_columns_to_host", "hbam_vcf_release", "hbam_vcf_gather_lines",
     "hbam_sam_decode_split", "hbam_sam_render",
     "hbam_fastq_decode_split", "hbam_qseq_decode_split", "hbam_frag_columns_to_host", "hbam_frag_release",
+    "hbam_frag_render",
 ]
 
 # hbam_read_fn: int64_t read(void* user, uint64_t offset, uint64_t len, uint8_t* dst)
@@ -190,6 +191,16 @@ class FragColumnsC(C.Structure):
                [("key_len", C.c_uint64), ("seq_len", C.c_uint64), ("qual_len", C.c_uint64),
                 ("text_base", C.c_uint64)]
 
+
+class FragTextC(C.Structure):
+    _fields_ = [
+        ("n_records", C.c_uint64), ("status", C.c_int32), ("pad", C.c_int32), ("err_record", C.c_uint64),
+        ("text_len", C.c_uint64), ("partial_len", C.c_uint64), ("text", C.c_void_p), ("line_off", C.c_void_p),
+    ]
+
+
+HBAM_FRAG_FASTQ, HBAM_FRAG_QSEQ = 0, 1
+HBAM_FRAG_USE_KEY, HBAM_FRAG_INDEX_DOTS = 1, 2
 
 # SequencedFragment's *_Present bits, in hbam_frag_columns.present's order
 FRAG_PRESENT = {"instrument": 0x001, "run": 0x002, "flowcell": 0x004, "lane": 0x008, "tile": 0x010,
@@ -326,6 +337,8 @@ def load(path=None):
                                              C.c_uint64, C.c_int32, C.c_int32, C.POINTER(FragColumnsC)]),
         "hbam_frag_columns_to_host": (C.c_int, [vp, C.POINTER(FragColumnsC), C.POINTER(FragColumnsC)]),
         "hbam_frag_release": (None, [vp, C.POINTER(FragColumnsC)]),
+        "hbam_frag_render": (C.c_int, [vp, C.POINTER(FragColumnsC), vp, C.c_int, C.c_uint64, vp, C.c_uint64,
+                                       C.c_int32, C.c_int32, C.c_uint32, C.POINTER(FragTextC)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name, None)
@@ -386,6 +399,26 @@ def _host_array(ptr, count, dt):
                                  shape=(count * np.dtype(dt).itemsize,)).view(dt).copy()
 
 
+class DeviceBuffer:
+    """Device bytes the library allocated (Context.upload: freed by free()) or owns (a view of a
+    call's output, valid until the context's next call of that kind): ptr, nbytes, and 64 readable
+    bytes behind them.  Accepted wherever a call takes bytes / numpy / a device tensor."""
+
+    def __init__(self, ctx, ptr, nbytes, owned):
+        self.ctx, self.ptr, self.nbytes, self.owned = ctx, int(ptr or 0), int(nbytes), owned
+
+    def free(self):
+        if self.owned and self.ptr and self.ctx.h:
+            self.ctx.L.hbam_device_free(self.ctx.h, C.c_void_p(self.ptr))
+        self.ptr, self.owned = 0, False
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Context:
     """One device context (hbam_ctx): a HIP stream plus device work buffers."""
 
@@ -427,6 +460,8 @@ class Context:
     def _ptr(data, output=False):
         """(pointer, length, on_device, keepalive) for bytes / numpy / torch cuda tensor.  An
         output buffer (the library writes into it) is never replaced by a padded copy."""
+        if isinstance(data, DeviceBuffer):
+            return C.c_void_p(data.ptr), data.nbytes, 1, data
         if hasattr(data, "data_ptr") and hasattr(data, "is_cuda"):
             if data.is_cuda:
                 # libhbam reads the raw pointer on its own stream: the bytes must be one dense
@@ -455,6 +490,15 @@ class Context:
             a = np.zeros(1, np.uint8)
             return C.c_void_p(a.ctypes.data), 0, 0, a
         return C.c_void_p(a.ctypes.data), a.size, 0, a
+
+    def upload(self, data):
+        """hbam_upload: a device copy of `data` (bytes / numpy) -> DeviceBuffer; free() it."""
+        p, n, dev, keep = self._ptr(data)
+        d = C.c_void_p()
+        rc = self.L.hbam_upload(self.h, p, n, C.byref(d))
+        if rc:
+            raise RuntimeError("hbam_upload failed (%d): %s" % (rc, self.last_error()))
+        return DeviceBuffer(self, d.value, n, True)
 
     def bgzf_compress(self, data, block_size=0, out=None):
         """BlockCompressedOutputStream over `data` (bytes / numpy / torch tensor, host or device)
@@ -1077,6 +1121,73 @@ class Context:
         self.L.hbam_frag_release(self.h, C.byref(h))
         out["timing"] = self.timing()
         return out
+
+    # ---- FASTQ / QSEQ output (hbam_fragtext.hip) ---------------------------------------------------
+    @staticmethod
+    def _frag_host_columns(cols):
+        """Host columns (frag_decode_split's dict form) as a FragColumnsC with host = 1 -> (struct,
+        the arrays it points into)."""
+        n = int(cols["n"])
+        h, keep = FragColumnsC(), []
+        h.n, h.host = n, 1
+
+        def put(name, dt, count):
+            a = np.ascontiguousarray(cols[name], dt).reshape(-1)
+            if a.size != count:
+                raise ValueError("column %s holds %d elements, not %d" % (name, a.size, count))
+            keep.append(a)
+            setattr(h, name, a.ctypes.data if a.size else None)
+            return a
+        put("present", np.uint32, n)
+        for name in ("run", "lane", "tile", "xpos", "ypos", "read", "filter_passed", "control"):
+            put(name, np.int32, n)
+        for name in ("instrument", "flowcell", "index"):
+            put(name, np.uint32, 2 * n)
+        for name in ("key", "seq", "qual"):
+            put(name + "_off", np.uint64, n + 1)
+            a = np.ascontiguousarray(cols[name], np.uint8).reshape(-1)
+            keep.append(a)
+            setattr(h, name, a.ctypes.data if a.size else None)
+            setattr(h, name + "_len", a.size)
+        return h, keep
+
+    def frag_render_device(self, cols, window, n=None, fmt=HBAM_FRAG_FASTQ, encoding=HBAM_QUAL_SANGER, flags=0,
+                           perm=None):
+        """hbam_frag_render -> (rc, device FragTextC).  cols: a device FragColumnsC (what
+        frag_decode_split_device left on this context) or host columns as a dict of numpy arrays
+        (frag_decode_split's form); window: the bytes the instrument / flowcell / index pairs point
+        into (bytes / numpy / a torch tensor, host or device); perm: a device pointer (int, ctypes
+        pointer or torch tensor) to n u32 record indices, device columns only."""
+        keep = None
+        if isinstance(cols, dict):
+            cols, keep = self._frag_host_columns(cols)
+        if n is None:
+            n = int(cols.n)
+        wp, wn, wdev, wkeep = self._ptr(window)
+        if perm is not None and hasattr(perm, "data_ptr"):
+            import torch
+            torch.cuda.current_stream(perm.device).synchronize()
+            perm_p = C.c_void_p(perm.data_ptr())
+        else:
+            perm_p = perm if isinstance(perm, (C.c_void_p, type(None))) else C.c_void_p(
+                perm if isinstance(perm, int) else C.cast(perm, C.c_void_p).value)
+        t = FragTextC()
+        rc = self.L.hbam_frag_render(self.h, C.byref(cols), wp, wdev, wn, perm_p, int(n), int(fmt), int(encoding),
+                                     int(flags), C.byref(t))
+        del keep, wkeep
+        return rc, t
+
+    def frag_render(self, cols, window, n=None, fmt=HBAM_FRAG_FASTQ, encoding=HBAM_QUAL_SANGER, flags=0, perm=None):
+        """hbam_frag_render and a host copy of what it wrote -> dict: n, status, err_record, text
+        (bytes: the complete records), partial (bytes: what the reference's stream already holds of
+        the failing record), line_off (uint64[n + 1]), timing."""
+        rc, t = self.frag_render_device(cols, window, n, fmt, encoding, flags, perm)
+        if rc:
+            return {"rc": rc, "error": self.last_error()}
+        k, tl, pl = int(t.n_records), int(t.text_len), int(t.partial_len)
+        both = self._d2h(t.text, tl + pl, np.uint8).tobytes()
+        return {"rc": 0, "n": k, "status": int(t.status), "err_record": int(t.err_record), "text": both[:tl],
+                "partial": both[tl:], "line_off": self._d2h(t.line_off, k + 1, np.uint64), "timing": self.timing()}
 
     # ---- SAM text (hbam_sam.hip) ------------------------------------------------------------------
     def sam_decode_split_device(self, data, start, length, data_start, table, n_ref, text_base=0, file_len=None):

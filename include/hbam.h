@@ -912,6 +912,70 @@ int hbam_frag_columns_to_host(hbam_ctx* ctx, const hbam_frag_columns* dev, hbam_
 /* frees a host copy's arrays; clears the struct either way */
 void hbam_frag_release(hbam_ctx* ctx, hbam_frag_columns* cols);
 
+/* ---- FASTQ and QSEQ output: FastqRecordWriter.write (FastqOutputFormat.java:94-147) and
+ * QseqRecordWriter.write (QseqOutputFormat.java:100-159) over hbam_frag_columns ---------------------
+ * The inverse of the two decodes above.  cols = device columns as a decode on this context left them
+ * (host = 0), or a host copy (host = 1), which the library uploads into context buffers.  window =
+ * the bytes the instrument / flowcell / index pairs point into, window_len < 2^32 of them, host
+ * (window_on_device == 0: uploaded) or device memory at any alignment; no byte at or past window_len
+ * is read.  Output record k is record perm[k] of cols (device u32[n]: a selection, a reorder,
+ * duplicates allowed; device columns only); perm == NULL means records 0 .. n - 1, n <= cols->n.
+ * n == 0 is legal and gives empty text.  format = HBAM_FRAG_*, encoding = HBAM_QUAL_* (of the text
+ * written; the pools hold Phred+33, as the reference's SequencedFragment does).  out's arrays are
+ * device arrays owned by the context until its next hbam_frag_render.
+ *
+ * HBAM_EINVAL (returned, nothing rendered): an unknown format, encoding or flag; perm with host
+ * columns; n >= 2^32 - 1; n > cols->n without perm; host key_off / seq_off / qual_off that do not
+ * ascend or leave their pool; a present host string pair that runs past window_len.  Device columns
+ * are trusted to be device arrays of cols->n records with 16 readable bytes behind each pool (what a
+ * decode leaves); their contents are checked per record in the sizes pass, where a perm entry >=
+ * cols->n, offsets that descend or leave the pool, a length above 2^31 - 1 or a present string pair
+ * past window_len ends the output there with status HBAM_EINVAL (the call returns HBAM_OK).
+ *
+ * FASTQ.  '@' id '\n' seq "\n+\n" qual '\n'.  With HBAM_FRAG_USE_KEY id = the record's key bytes
+ * (write(key != null, ...)); otherwise makeId: instrument:run:flowcell:lane:tile:x:y, a space,
+ * read:F:control:index.  A field whose present bit is clear is empty; integers as Integer.toString
+ * ('-', no padding, down to -2147483648); F = 'N' when filter_passed is absent or non-zero, else 'Y';
+ * control absent = "0"; index absent = empty, with HBAM_FRAG_INDEX_DOTS each '.' in it as 'N' (the
+ * raw QSEQ field, see the columns above).  The strings' bytes are written as they are
+ * (makeId(...).getBytes() uses the platform charset: unpinned).  HBAM_QUAL_SANGER: the quality bytes
+ * verbatim, unchecked.  HBAM_QUAL_ILLUMINA: SequencedFragment.convertQuality Sanger -> Illumina
+ * (SequencedFragment.java:234-247): every byte, as a signed byte, must lie in [33, 126], else
+ * HBAM_ESEQFORMAT; the byte written is (uint8_t)(b + 31), so 96 .. 126 leave as 127 .. 157 unchecked.
+ * The reference has then already written "@id\nseq\n+\n": partial_len is that length and those bytes
+ * stand at text[text_len, text_len + partial_len).
+ *
+ * QSEQ.  instrument \t run \t lane \t tile \t x \t y \t index \t read \t seq \t qual \t filter \n.
+ * index: absent or empty = "0", else 'N' as '.' (a '.' stays, with or without INDEX_DOTS); seq: 'N'
+ * as '.'; filter '1' when absent or non-zero, else '0'; key, flowcell and control are not written.
+ * HBAM_QUAL_SANGER: quality verbatim.  HBAM_QUAL_ILLUMINA: b + 31; a result above 126 (b > 95) is
+ * HBAM_ERUNTIME, there is no lower bound.  The reference works on the decoded String: a byte >= 0x80
+ * in seq or qual is HBAM_EUNSUPPORTED (Text decode / encode are not restated), which wins over
+ * HBAM_ERUNTIME in the same record.  Nothing of a failing record is written: partial_len = 0.
+ *
+ * The first failing record in output order ends the call: status, err_record = n_records = its
+ * output position, text_len = line_off[n_records]; the records before it stand.
+ * Timing: total_ms, walk_ms = sizes + scan, huffman_ms = the per-record pass (id line / leading
+ * fields, separators, filter), resolve_ms = the sequence / quality pass, n_records, ubuf_bytes = the
+ * text bytes. */
+#define HBAM_FRAG_FASTQ 0
+#define HBAM_FRAG_QSEQ 1
+#define HBAM_FRAG_USE_KEY 1u    /* FASTQ: the id line is '@' + the record's key */
+#define HBAM_FRAG_INDEX_DOTS 2u /* the index column is a raw QSEQ field: '.' reads as 'N' */
+typedef struct hbam_frag_text {
+  uint64_t n_records;   /* complete records in text */
+  int32_t status;       /* HBAM_OK or what write() raises at record err_record */
+  int32_t pad;
+  uint64_t err_record;  /* output position */
+  uint64_t text_len;    /* bytes of the n_records complete records */
+  uint64_t partial_len; /* bytes of record err_record the reference's stream already holds when it throws */
+  uint8_t* text;        /* device, owned by the context until the next render */
+  uint64_t* line_off;   /* device u64[n_records + 1] */
+} hbam_frag_text;
+int hbam_frag_render(hbam_ctx* ctx, const hbam_frag_columns* cols, const uint8_t* window, int window_on_device,
+                     uint64_t window_len, const uint32_t* perm, uint64_t n, int32_t format, int32_t encoding,
+                     uint32_t flags, hbam_frag_text* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -106,6 +106,11 @@ public final class Hbam implements AutoCloseable {
   // line_off, n_deferred, deferred: 64 bytes)
   static final MethodHandle SAM_RENDER = fn("hbam_sam_render",
       FunctionDescriptor.of(I, A, A, A, A, J, I, A, A, I, A));
+  // FASTQ / QSEQ output (FastqOutputFormat, QseqOutputFormat): hbam_frag_columns on the device or the
+  // host + the window of their strings -> the writers' text; out is an hbam_frag_text (n_records,
+  // status, pad, err_record, text_len, partial_len, text, line_off: 56 bytes)
+  static final MethodHandle FRAG_RENDER = fn("hbam_frag_render",
+      FunctionDescriptor.of(I, A, A, A, I, J, A, J, I, I, I, A));
 
   /** hbam_bcf_header: n_contig, n_sample, n_dict, bgzf, header_len, first_voffset (32 bytes). */
   public static final StructLayout BCF_HEADER = MemoryLayout.structLayout(

@@ -1,0 +1,176 @@
+"""FASTQ / QSEQ output, CPU side: the tests' restatement of the two writers (tests/seqfrag_out_ref.py)
+against the recorded assertions of the reference's own tests, the device's per-record rules
+(csrc/frag_text.h) run by a sanitizer-built host program against that restatement, the writers'
+setConf without a device, and the render-after-decode identities on the reference's own files."""
+import os
+import random
+import subprocess
+
+import pytest
+
+import seqfrag_out_cases as cases
+import seqfrag_out_ref as ref
+import seqfrag_ref
+from conftest import GOLDEN, ROOT
+
+SEQFRAG = os.path.join(GOLDEN, "seqfrag")
+# (file, source format, source Illumina, use_key): render-after-decode gives the file back + b"\n"
+IDENTITIES = [("oneFastq.fastq", "fastq", False, True), ("illuminaFastq.fastq", "fastq", False, True),
+              ("twoFastqWithIllumina.fastq", "fastq", False, True), ("illuminaFastq.fastq", "fastq", False, False),
+              ("twoFastqWithIllumina.fastq", "fastq", False, False), ("oneQseq.qseq", "qseq", True, False),
+              ("twoQseq.qseq", "qseq", True, False)]
+
+
+def golden_file(name):
+    with open(os.path.join(SEQFRAG, name), "rb") as f:
+        return f.read()
+
+
+def ref_decode(data, fmt, illumina):
+    run = seqfrag_ref.run_fastq if fmt == "fastq" else seqfrag_ref.run_qseq
+    return run(data, 0, len(data), illumina=illumina)
+
+
+def test_import_exports_the_output_classes():
+    import hadoop_bam
+    for name in ("FastqOutputFormat", "FastqRecordWriter", "QseqOutputFormat", "QseqRecordWriter", "convert"):
+        assert getattr(hadoop_bam, name)
+    assert "hbam_frag_render" in hadoop_bam._lib.EXPORTS
+    assert hadoop_bam.FastqOutputFormat.CONF_BASE_QUALITY_ENCODING == "hbam.fastq-output.base-quality-encoding"
+    assert hadoop_bam.FastqOutputFormat.CONF_BASE_QUALITY_ENCODING_DEFAULT == "sanger"
+    assert hadoop_bam.QseqOutputFormat.CONF_BASE_QUALITY_ENCODING == "hbam.qseq-output.base-quality-encoding"
+    assert hadoop_bam.QseqOutputFormat.CONF_BASE_QUALITY_ENCODING_DEFAULT == "illumina"
+
+
+@pytest.mark.parametrize("fmt", ["fastq", "qseq"])
+def test_restatement_meets_the_reference_assertions(fmt):
+    section = cases.expected()[fmt]
+    assert section["conf_key"] == ref.CONF_KEY[fmt]
+    seen = set()
+    for case in section["cases"]:
+        seen.add(case["test"])
+        if case.get("raises"):
+            with pytest.raises(ref.RuntimeException):
+                ref.set_conf(case["conf"], fmt)
+            continue
+        illumina = ref.set_conf(case["conf"], fmt)
+        out = bytearray()
+        if not case.get("close_only"):
+            f = cases.case_fragment(section, case)
+            (ref.fastq_write if fmt == "fastq" else ref.qseq_write)(out, case["key"], f, illumina)
+        cases.check_case(case, out)
+    want = {"fastq": {"testSimple", "testNullControlNumber", "testNullFilter", "testCustomId",
+                      "testBaseQualitiesInIllumina", "testConfigureOutputInSanger", "testBadConfig", "testClose"},
+            "qseq": {"testSimple", "testConvertUnknowns", "testConvertUnknownsInIndexSequence", "testBaseQualities",
+                     "testConfigureOutputInSanger", "testNoIndex", "testClose"}}[fmt]
+    assert seen == want
+
+
+def test_set_conf_raises_without_a_device():
+    from hadoop_bam import FastqRecordWriter, QseqRecordWriter
+    from hadoop_bam.fastq import RuntimeException
+    for cls in (FastqRecordWriter, QseqRecordWriter):
+        with pytest.raises(RuntimeException):
+            cls({cls.CONF_BASE_QUALITY_ENCODING: "blalbal"}, None)
+        w = cls({}, None)
+        assert w.baseQualityFormat == ("Sanger" if cls is FastqRecordWriter else "Illumina")
+        with pytest.raises(RuntimeException):
+            w.setConf({cls.CONF_BASE_QUALITY_ENCODING: "blalbal"})
+        w.setConf({cls.CONF_BASE_QUALITY_ENCODING: "illumina"})
+        assert w.baseQualityFormat == "Illumina"
+
+
+@pytest.mark.parametrize("name,fmt,illumina,use_key", IDENTITIES)
+def test_render_after_decode_gives_the_file_back(name, fmt, illumina, use_key):
+    data = golden_file(name)
+    dec = ref_decode(data, fmt, illumina)
+    assert dec["status"] == 0 and dec["n"] >= 1
+    got = ref.render(dec["records"], fmt, illumina, use_key)
+    assert got["status"] == 0
+    assert got["text"] == data + b"\n"
+
+
+def test_restatement_partial_and_status_rules():
+    r = random.Random(3)
+    recs = [cases.short_record(r) for _ in range(5)]
+    bad = cases.with_qual_byte(recs, 2, -1, 127)
+    got = ref.render(bad, "fastq", True, True)
+    assert (got["status"], got["err_record"], got["n"]) == (ref.ESEQFORMAT, 2, 2)
+    assert got["partial"] == b"@" + bad[2]["key"] + b"\n" + bad[2]["seq"] + b"\n+\n"
+    assert got["text"] == ref.render(bad[:2], "fastq", True, True)["text"]
+    assert ref.render(bad, "fastq", False, True)["status"] == 0
+    got = ref.render(cases.with_qual_byte(recs, 4, 0, 96), "qseq", True)
+    assert (got["status"], got["err_record"], got["partial"]) == (ref.ERUNTIME, 4, b"")
+    both = cases.with_qual_byte(cases.with_qual_byte(recs, 1, 0, 100), 1, -1, 0x80)
+    assert ref.render(both, "qseq", True)["status"] == ref.EUNSUPPORTED
+    assert ref.render(cases.with_qual_byte(recs, 0, 0, 0x20), "qseq", True)["status"] == 0
+
+
+@pytest.fixture(scope="module")
+def host_program(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("frag_text_host") / "frag_text_host")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "hadoop-bam_amd", "csrc"),
+                    "-o", exe, os.path.join(ROOT, "tools", "frag_text_host.cpp")], check=True)
+    return exe
+
+
+def run_host(exe, tmp_path, records, fmt, encoding, flags):
+    src, out = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    with open(src, "wb") as f:
+        f.write(cases.host_input(cases.columns(records), fmt, encoding, flags))
+    subprocess.run([exe, src, out], check=True)
+    with open(out, "rb") as f:
+        return cases.host_output(f.read(), len(records))
+
+
+def status_of(fmt, flags):
+    if flags == 0:
+        return 0
+    if fmt == cases.FASTQ:
+        return ref.ESEQFORMAT
+    return ref.EUNSUPPORTED if flags & 2 else ref.ERUNTIME
+
+
+def test_device_record_rules_on_the_cpu_match_the_restatement(host_program, tmp_path):
+    """csrc/frag_text.h is host-and-device C++: tools/frag_text_host.cpp, a stand-alone program built
+    here with the address and undefined-behaviour sanitizers, runs every record through the rules
+    the kernels run (both passes, the bulk region unit by unit on the output's 16-byte grid) over
+    pools held in heap blocks of exactly their bytes + 16 and a window of exactly its bytes.  The
+    field grid (all 2,048 present masks) for both formats, both encodings and every flag
+    combination, then the quality and sequence edge bytes: every status and every byte must be the
+    restatement's."""
+    grid = cases.grid_records()
+    for fmt in (cases.FASTQ, cases.QSEQ):
+        name = "fastq" if fmt == cases.FASTQ else "qseq"
+        for encoding in (cases.SANGER, cases.ILLUMINA):
+            for flags in (0, 1, 2, 3):
+                got = run_host(host_program, tmp_path, grid, fmt, encoding, flags)
+                for k, (f, (bad, text)) in enumerate(zip(grid, got)):
+                    g = dict(f)
+                    if flags & cases.INDEX_DOTS and g["index"] is not None:
+                        g["index"] = g["index"].replace(b".", b"N")
+                    want = ref.render([g], name, bool(encoding), bool(flags & cases.USE_KEY))
+                    assert bad == 0 and want["status"] == 0, (name, encoding, flags, k)
+                    assert text == want["text"], (name, encoding, flags, k, text[:100], want["text"][:100])
+            r = random.Random(11)
+            base = [cases.short_record(r, ls) for ls in (0, 1, 5, 16, 17, 40, 33)]
+            edge = []
+            for byte in (0, 10, 32, 33, 46, 78, 95, 96, 126, 127, 0x80, 0xff):
+                for where in (0, -1):
+                    for at in (1, 3, 6):
+                        edge.append(cases.with_qual_byte(base, at, where, byte)[at])
+            hi = dict(base[4])
+            hi["seq"] = b"AC\x80GT" + hi["seq"]
+            edge.append(hi)
+            hi = dict(base[5])
+            hi["qual"] = b"\x7e" + hi["qual"][1:-1] + b"\x81"  # a byte > 95 before one >= 0x80
+            edge.append(hi)
+            got = run_host(host_program, tmp_path, edge, fmt, encoding, cases.USE_KEY)
+            for k, (f, (bad, text)) in enumerate(zip(edge, got)):
+                want = ref.render([f], name, bool(encoding), True)
+                assert status_of(fmt, bad) == want["status"], (name, encoding, k, bad, want["status"])
+                if want["status"] == 0:
+                    assert text == want["text"], (name, encoding, k)
+                elif fmt == cases.FASTQ:
+                    assert text[:len(want["partial"])] == want["partial"], (name, encoding, k)
