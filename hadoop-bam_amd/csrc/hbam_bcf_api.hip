@@ -165,10 +165,14 @@ int bcf_cols(hbam_ctx* c, uint64_t n, BcfCols* k) {
 
 }  // namespace
 
-extern "C" int hbam_bcf_parse_header(hbam_ctx* c, const uint8_t* file, uint64_t len, hbam_bcf_header* out) {
-  if (!c || !file || !out) return HBAM_EINVAL;
+// BCF2Codec.readHeader over the file's first bytes -> *out and the uncompressed stream's first
+// header_len bytes at *stream: the file itself, or *ubytes, the leading BGZF blocks inflated on the
+// device (hbam_bcf_parse_header, hbam_bcf_header_text)
+static int bcf_header_stream(hbam_ctx* c, const uint8_t* file, uint64_t len, hbam_bcf_header* out,
+                             std::vector<uint8_t>* ubytes, const uint8_t** stream) {
   memset(out, 0, sizeof *out);
   HIPCHK(c, hipSetDevice(c->device));
+  *stream = file;
   if (!bgzf_magic(file, len)) {
     out->bgzf = 0;
     int rc = bcf_header_text(file, len, out);
@@ -177,7 +181,7 @@ extern "C" int hbam_bcf_parse_header(hbam_ctx* c, const uint8_t* file, uint64_t 
   }
   out->bgzf = 1;
   // inflate the leading blocks on the device until the header text is complete
-  std::vector<uint8_t> u;
+  std::vector<uint8_t>& u = *ubytes;
   std::vector<uint64_t> ustart;  // stream position of each block, for first_voffset
   std::vector<uint64_t> coffs;
   uint64_t p = 0;
@@ -228,7 +232,15 @@ extern "C" int hbam_bcf_parse_header(hbam_ctx* c, const uint8_t* file, uint64_t 
       break;
     }
   }
+  *stream = u.data();
   return HBAM_OK;
+}
+
+extern "C" int hbam_bcf_parse_header(hbam_ctx* c, const uint8_t* file, uint64_t len, hbam_bcf_header* out) {
+  if (!c || !file || !out) return HBAM_EINVAL;
+  std::vector<uint8_t> u;
+  const uint8_t* stream;
+  return bcf_header_stream(c, file, len, out, &u, &stream);
 }
 
 extern "C" uint64_t hbam_guess_bcf_window_len(uint64_t file_len, int64_t beg, int64_t end, int bgzf) {

@@ -227,6 +227,19 @@ enum BufId {
   B_ST_DEFERRED,
   B_ST_SMALL,
   B_ST_TEXT,
+  // VCF text output (hbam_vcftext.hip)
+  B_VT_META,
+  B_VT_DATA,
+  B_VT_RECOFF,
+  B_VT_LEN,
+  B_VT_STATUS,
+  B_VT_DFLAG,
+  B_VT_SITE,
+  B_VT_LINEOFF,
+  B_VT_DPOS,
+  B_VT_DEFERRED,
+  B_VT_SMALL,
+  B_VT_TEXT,
   // FASTQ / QSEQ (hbam_fastq.hip)
   B_FQ_CAND,
   B_FQ_OUT,
@@ -2736,3 +2749,4 @@ extern "C" int64_t hbam_bgzf_compress(hbam_ctx* c, const uint8_t* src, int src_o
 #include "hbam_samtext.hip"
 #include "hbam_fastq.hip"
 #include "hbam_fragtext.hip"
+#include "hbam_vcftext.hip"

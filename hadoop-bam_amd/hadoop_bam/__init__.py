@@ -5,7 +5,8 @@ SAMRecordWritable, BAMSplitGuesser, util.BGZFSplitGuesser, util.BGZFBlockIndexer
 shuffle sort (cli/plugins/Sort) and its BAM output (BAMRecordWriter, KeyIgnoringBAMOutputFormat,
 util.SAMOutputPreparer, cli.Utils.mergeSAMInto) and its SAM text output (SAMRecordWriter,
 KeyIgnoringAnySAMOutputFormat, the View plugin), and the read formats FASTQ and QSEQ in both
-directions (FastqInputFormat, QseqInputFormat, FastqOutputFormat, QseqOutputFormat); compute runs
+directions (FastqInputFormat, QseqInputFormat, FastqOutputFormat, QseqOutputFormat), and VCF text
+output over BCF records (VCFRecordWriter, KeyIgnoringVCFOutputFormat, vcf_sort); compute runs
 in libhbam.so (HIP, gfx950) through the C ABI of include/hbam.h.
 """
 from ._lib import Context, HbamUnavailable, load  # noqa: F401
@@ -28,3 +29,6 @@ from .fastq import (  # noqa: F401
     QseqInputFormat, QseqRecordReader, SequencedFragment)
 from .fastq_text import (  # noqa: F401
     FastqOutputFormat, FastqRecordWriter, QseqOutputFormat, QseqRecordWriter, convert)
+from .vcf_text import (  # noqa: F401
+    KeyIgnoringVCFOutputFormat, KeyIgnoringVCFRecordWriter, VCFHeader, VCFOutputFormat, VCFRecordWriter,
+    VCFUnsupportedException, read_vcf_header_from)

@@ -70,6 +70,7 @@ EXPORTS = [
     "hbam_sam_decode_split", "hbam_sam_render",
     "hbam_fastq_decode_split", "hbam_qseq_decode_split", "hbam_frag_columns_to_host", "hbam_frag_release",
     "hbam_frag_render",
+    "hbam_bcf_header_text", "hbam_vcf_render",
 ]
 
 # hbam_read_fn: int64_t read(void* user, uint64_t offset, uint64_t len, uint8_t* dst)
@@ -180,6 +181,19 @@ class SamTextC(C.Structure):
         ("text_len", C.c_uint64), ("text", C.c_void_p), ("line_off", C.c_void_p), ("n_deferred", C.c_uint64),
         ("deferred", C.c_void_p),
     ]
+
+
+class VcfMetaC(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("contig_names", "contig_off", "dict_names", "dict_off", "dict_rank",
+                                          "dict_flags", "dict_number")]
+
+
+# hbam_vcf_meta.dict_flags / dict_number (include/hbam.h)
+HBAM_VCF_HAS_INFO, HBAM_VCF_INFO_FLAG, HBAM_VCF_HAS_FORMAT, HBAM_VCF_KIND_SHIFT = 1, 2, 4, 4
+HBAM_VCF_KINDS = {"GT": 1, "DP": 2, "GQ": 3, "AD": 4, "PL": 5, "FT": 6}
+HBAM_VCF_NUMBER = {".": -1, "A": -2, "R": -3, "G": -4}
+HBAM_VCF_MAX_INFO, HBAM_VCF_MAX_FILTER, HBAM_VCF_MAX_FORMAT, HBAM_VCF_MAX_PLOIDY = 64, 64, 16, 16
+HBAM_VCF_WAVE_SAMPLES = 64
 
 
 class FragColumnsC(C.Structure):
@@ -331,6 +345,9 @@ def load(path=None):
                                             C.c_uint64, C.c_uint64, vp, C.c_uint32, vp, C.c_uint64, C.c_int32,
                                             C.POINTER(Columns)]),
         "hbam_sam_render": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_int, vp, vp, C.c_int32, C.POINTER(SamTextC)]),
+        "hbam_bcf_header_text": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "hbam_vcf_render": (C.c_int, [vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_int, C.POINTER(BcfHeaderC),
+                                      C.POINTER(VcfMetaC), C.POINTER(SamTextC)]),
         "hbam_fastq_decode_split": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
                                               C.c_uint64, C.c_int32, C.c_int32, C.POINTER(FragColumnsC)]),
         "hbam_qseq_decode_split": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
@@ -1256,6 +1273,78 @@ class Context:
         (bytes; a deferred line is empty), line_off (uint64[n + 1]), deferred (uint32, ascending
         output positions), timing."""
         rc, t = self.sam_render_device(ubuf, rec_off, n, names, perm, on_device)
+        if rc:
+            return {"rc": rc, "error": self.last_error()}
+        k = int(t.n_records)
+        return {"rc": 0, "n": k, "status": int(t.status), "err_record": int(t.err_record),
+                "text": self._d2h(t.text, int(t.text_len), np.uint8).tobytes(),
+                "line_off": self._d2h(t.line_off, k + 1, np.uint64),
+                "deferred": self._d2h(t.deferred, int(t.n_deferred), np.uint32), "timing": self.timing()}
+
+    # ---- VCF text output (hbam_vcftext.hip) --------------------------------------------------------
+    def bcf_header_text(self, file_prefix):
+        """hbam_bcf_header_text: the VCF header text of a BCF file (BGZF or plain) from its first bytes
+        -> bytes, or an error code (HBAM_EMORE: the header runs past the prefix)."""
+        a = np.ascontiguousarray(np.frombuffer(bytes(file_prefix), np.uint8))
+        n = C.c_uint64(0)
+        rc = self.L.hbam_bcf_header_text(self.h, C.c_void_p(a.ctypes.data), a.size, None, 0, C.byref(n))
+        if rc:
+            return rc
+        out = np.zeros(max(int(n.value), 1), np.uint8)
+        rc = self.L.hbam_bcf_header_text(self.h, C.c_void_p(a.ctypes.data), a.size, C.c_void_p(out.ctypes.data),
+                                         int(n.value), C.byref(n))
+        if rc:
+            return rc
+        return out[:int(n.value)].tobytes()
+
+    def bcf_decode_split_device(self, data, h, start, end_or_len, comp_base=0, file_len=None):
+        """hbam_bcf_decode_split -> (rc, device BcfColumnsC): nothing is copied; the arrays are the
+        context's until its next decode."""
+        p, n, dev, keep = self._ptr(data)
+        if file_len is None:
+            file_len = comp_base + n
+        d = BcfColumnsC()
+        hc = self._bcf_hdr(h)
+        rc = self.L.hbam_bcf_decode_split(self.h, p, dev, int(comp_base), n, int(file_len), C.byref(hc),
+                                          int(start), int(end_or_len), C.byref(d))
+        del keep
+        return rc, d
+
+    def vcf_render_device(self, data, data_len, rec_off, n, h, meta, perm=None, on_device=True):
+        """hbam_vcf_render -> (rc, device SamTextC).  on_device: data / rec_off / perm are device
+        pointers (a BCF decode's columns, hbam_sort_keys' permutation); else data is host bytes and
+        rec_off a host uint64 array of n offsets.  h = the header counts (bcf_parse_header's dict),
+        meta = the dict of host arrays VCFHeader.meta() builds."""
+        vp = C.c_void_p
+        m = VcfMetaC()
+        keep = [np.ascontiguousarray(meta[k]) for k in ("contig_names", "contig_off", "dict_names", "dict_off",
+                                                        "dict_rank", "dict_flags", "dict_number")]
+        for (name, _), a in zip(VcfMetaC._fields_, keep):
+            setattr(m, name, a.ctypes.data)
+        hc = self._bcf_hdr(dict(h, bgzf=0, header_len=0))
+        t = SamTextC()
+        if on_device:
+            args = [C.cast(x, vp) if not isinstance(x, (int, type(None))) else vp(x) for x in (data, rec_off, perm)]
+        else:
+            if perm is not None:
+                raise ValueError("perm needs device arguments")
+            ro = np.ascontiguousarray(rec_off, np.uint64)
+            if len(ro) < n:
+                raise ValueError("rec_off must hold n offsets")
+            ub = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data)
+            data_len = ub.size
+            keep += [ro, ub]
+            args = [vp(ub.ctypes.data if ub.size else 0), vp(ro.ctypes.data), vp(None)]
+        rc = self.L.hbam_vcf_render(self.h, args[0], int(data_len), args[1], args[2], int(n), int(bool(on_device)),
+                                    C.byref(hc), C.byref(m), C.byref(t))
+        del keep
+        return rc, t
+
+    def vcf_render(self, data, data_len, rec_off, n, h, meta, perm=None, on_device=True):
+        """hbam_vcf_render and a host copy of what it wrote -> dict: n, status, err_record, text
+        (bytes; a deferred line is empty), line_off (uint64[n + 1]), deferred (uint32, ascending
+        output positions), timing."""
+        rc, t = self.vcf_render_device(data, data_len, rec_off, n, h, meta, perm, on_device)
         if rc:
             return {"rc": rc, "error": self.last_error()}
         k = int(t.n_records)

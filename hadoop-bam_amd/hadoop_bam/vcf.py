@@ -239,12 +239,16 @@ def vcf_sort(in_path, out_path, conf=None, data=None):
     """The vcf-sort plugin with -o (cli/plugins/VCFSort.java): the header's bytes as they are, then
     the data lines in the order of their keys, each ended by a newline.  The whole file is decoded
     on one GPU, the keys go through the stable hbam_sort_keys (equal keys keep input order) and
-    hbam_vcf_gather_lines packs the lines.  Output is VCF text only: re-encoding through htsjdk's
-    writers (and so a .bcf output) is not restated."""
+    hbam_vcf_gather_lines packs the lines.  A BCF input (BGZF or plain, by its first byte) is decoded
+    on the device as one split, its keys sorted the same way, and its records rendered as VCF lines
+    where they stand (VCFRecordWriter.write_device with the permutation).  Output is VCF text only: a
+    .bcf output (BCFRecordWriter) is not restated."""
     import ctypes as C
     if VCFFormat.inferFromFilePath(out_path) == VCFFormat.BCF:
         raise NotImplementedError("vcf_sort writes VCF text only: %s" % out_path)
     ctx = context(conf)
+    if VCFFormat.inferFromData(data if data is not None else in_path) == VCFFormat.BCF:
+        return _vcf_sort_bcf(ctx, data if data is not None else in_path, out_path)
     ss = SeekableFile(data if data is not None else in_path)
     header, contigs, data_start = read_vcf_header(ss, in_path)
     if data_start >= ss.length or ss.read_at(data_start, 1) == b"#":
@@ -270,3 +274,39 @@ def vcf_sort(in_path, out_path, conf=None, data=None):
         f.write(lines)
     _raise(int(d.status), "VCFCodec.decode")  # a line that does not decode fails the job
     return {"n": n, "sort_ms": sort_ms, "gather_ms": gather_ms}
+
+
+def _vcf_sort_bcf(ctx, src, out_path):
+    """vcf_sort over a BCF input: one whole-file hbam_bcf_decode_split, the stable hbam_sort_keys on
+    the keys, then hbam_vcf_render over the device columns in that order; only the text (and the
+    records the device defers) leave the device."""
+    import ctypes as C
+    from .bcf import read_bcf_header
+    from .vcf_text import VCFRecordWriter, read_vcf_header_from
+    header = read_vcf_header_from(src, ctx)
+    ss = SeekableFile(src)
+    h = read_bcf_header(ss, ctx)
+    body = ss.read_at(0, ss.length)
+    ss.close()
+    if h["bgzf"]:
+        rc, d = ctx.bcf_decode_split_device(body, h, h["first_voffset"], (len(body) << 16) | 0xffff)
+    else:
+        rc, d = ctx.bcf_decode_split_device(body, h, 0, len(body))
+    raise_for(rc, ctx.last_error())
+    n = int(d.n_records)
+    perm = C.c_void_p()
+    rc = ctx.L.hbam_device_alloc(ctx.h, 4 * max(n, 1), C.byref(perm))
+    raise_for(rc, ctx.last_error())
+    try:
+        rc = ctx.L.hbam_sort_keys(ctx.h, d.key, n, None, perm)
+        raise_for(rc, ctx.last_error())
+        sort_ms = ctx.timing()["total_ms"]
+        w = VCFRecordWriter(out_path, header, True, ctx)
+        try:
+            res = w.write_device(d, perm, n)
+        finally:
+            w.close()
+    finally:
+        ctx.L.hbam_device_free(ctx.h, perm)
+    _raise(int(d.status), "BCF2Codec.decode")  # a record that does not decode fails the job
+    return {"n": n, "sort_ms": sort_ms, "render_ms": res["timing"]["total_ms"], "deferred": len(res["deferred"])}

@@ -792,6 +792,125 @@ int hbam_sam_render(hbam_ctx* ctx, const uint8_t* ubuf, const uint64_t* rec_off,
                     uint64_t n, int on_device, const uint8_t* names, const uint32_t* name_off,
                     int32_t n_ref, hbam_sam_text* out);
 
+/* ---- VCF text out of BCF records on the device: VCFRecordWriter / KeyIgnoringVCFRecordWriter
+ * (VCFRecordWriter.java), VCFOutputFormat / KeyIgnoringVCFOutputFormat and the VCF half of
+ * VCFSort -o out.vcf over a BCF input --------------------------------------------------------------
+ * The VCF header text of a BCF file (BGZF or plain) in file[0, len), without the trailing NULs:
+ * out == NULL only asks for *text_len; else at most cap bytes are written (HBAM_EINVAL when cap is
+ * smaller than the text).  HBAM_EMORE and the other codes as hbam_bcf_parse_header, whose inflate
+ * path this call uses. */
+int hbam_bcf_header_text(hbam_ctx* ctx, const uint8_t* file, uint64_t len, uint8_t* out, uint64_t cap,
+                         uint64_t* text_len);
+
+/* What the renderer needs from the header besides hbam_bcf_header: host arrays, copied to the
+ * device by the call.  The dictionary is the one hbam_bcf_parse_header counts (PASS, then the
+ * FILTER / INFO / FORMAT IDs by first occurrence). */
+#define HBAM_VCF_HAS_INFO 1u     /* dict_flags: the entry has an INFO line */
+#define HBAM_VCF_INFO_FLAG 2u    /* ... and that line is Type=Flag or Number=0 */
+#define HBAM_VCF_HAS_FORMAT 4u   /* the entry has a FORMAT line */
+#define HBAM_VCF_KIND_SHIFT 4    /* (dict_flags >> 4) & 7: the FORMAT line's kind */
+#define HBAM_VCF_KIND_GENERIC 0u
+#define HBAM_VCF_KIND_GT 1u
+#define HBAM_VCF_KIND_DP 2u
+#define HBAM_VCF_KIND_GQ 3u
+#define HBAM_VCF_KIND_AD 4u
+#define HBAM_VCF_KIND_PL 5u
+#define HBAM_VCF_KIND_FT 6u
+#define HBAM_VCF_NUMBER_DOT (-1) /* dict_number: the FORMAT line's Number, a fixed integer >= 0 or one of these */
+#define HBAM_VCF_NUMBER_A (-2)
+#define HBAM_VCF_NUMBER_R (-3)
+#define HBAM_VCF_NUMBER_G (-4)
+/* The device's caps: a record above one of them is deferred to the host renderer. */
+#define HBAM_VCF_MAX_INFO 64u    /* INFO pairs */
+#define HBAM_VCF_MAX_FILTER 64u  /* FILTER entries */
+#define HBAM_VCF_MAX_FORMAT 16u  /* genotype fields */
+#define HBAM_VCF_MAX_PLOIDY 16u  /* alleles per call (the GT vector's length) */
+/* Records of this many samples or more are rendered by a wave (lanes stride the samples), records
+ * of fewer by one lane. */
+#define HBAM_VCF_WAVE_SAMPLES 64u
+typedef struct hbam_vcf_meta {
+  const uint8_t* contig_names;  /* the ##contig IDs back to back */
+  const uint32_t* contig_off;   /* u32[n_contig + 1] */
+  const uint8_t* dict_names;    /* the dictionary strings back to back ("PASS" first) */
+  const uint32_t* dict_off;     /* u32[n_dict + 1] */
+  const uint32_t* dict_rank;    /* u32[n_dict]: the entry's rank in ascending String.compareTo order */
+  const uint32_t* dict_flags;   /* u32[n_dict]: HBAM_VCF_* bits and the FORMAT kind */
+  const int32_t* dict_number;   /* i32[n_dict]: the FORMAT line's Number */
+} hbam_vcf_meta;
+
+/* BCF2 records -> VCF text lines, the inverse direction of hbam_bcf_decode_split.  data / rec_off as
+ * in hbam_bcf_columns: record i is l_shared | l_indiv | site | genotypes at data[rec_off[i]], data_len
+ * the bytes of data, with 64 readable bytes behind them.  Output line k is record perm[k] (device
+ * u32[n]; an index may repeat); perm == NULL is the identity.  on_device == 0: data and rec_off
+ * (u64[n]) are host arrays that the library uploads with the slack, and perm must be NULL.  hdr = the
+ * file's hbam_bcf_header, meta as above (host).  n == 0 is legal.  out mirrors hbam_sam_render's:
+ * device arrays owned by the context until its next call; a DEFERRED line is empty in text and its
+ * output position is listed in deferred; the caller renders it (hadoop_bam.vcf_text.render_record) and
+ * splices it in.
+ *
+ * The rules (htsjdk's VCFEncoder and BCF2 decoders, restated from memory, parity unpinned):
+ * Line: CHROM \t POS \t ID \t REF \t ALT \t QUAL \t FILTER \t INFO [\t FORMAT (\t sample)*] \n.
+ * Typed values: descriptor and long counts as hbam_bcf_decode_split reads them.  Integer types 1 / 2 /
+ *   3 have the missing value 0x80 / 0x8000 / 0x80000000; every other integer is a number, the
+ *   end-of-vector codes included.  Float: 0x7F800001 is missing, anything else is the float.
+ *   decodeTypedValue: count 0 is null; type 7 is the bytes with trailing NULs dropped, empty is null,
+ *   and a string beginning with ',' is a list: that first comma is dropped; count 1 is the value, null
+ *   when missing; count above 1 is the values with EVERY missing one dropped, all missing is null.
+ *   decodeIntArray (GT, AD, PL): the values before the first missing one, none is null.
+ * CHROM contigs[chrom]; POS pos + 1; ID the string, '.' when null; REF allele 0; ALT alleles 1.. joined
+ *   by ',', '.' when n_allele == 1.  An allele is symbolic if it starts with '<' and ends with '>', or
+ *   contains '[' or ']', or starts or ends with '.'; other alleles have a-z upper-cased.  An empty
+ *   allele: HBAM_ERUNTIME.
+ * QUAL: the missing float is '.'; else d = ((double)q / -10.0) * -10.0 + 0.0 written with %.2f
+ *   (HALF_UP), a trailing ".00" dropped ("80", "29.60").
+ * FILTER: null is '.'; else the distinct dictionary strings, ascending, joined by ';' (offset 0 prints
+ *   PASS).
+ * INFO, per (key, value): a key without an INFO line: HBAM_ETRIBBLE; a Flag-typed key takes the value
+ *   true whatever was stored.  Ascending by key, joined by ';', '.' when there are none.  KEY alone
+ *   when the text value is empty (true) or the line is Number=0, else KEY=value.  Value text: null
+ *   '.', an integer decimal, a string its bytes, a list its elements joined by ',', a float through
+ *   formatVCFDouble: d >= 1 %.2f; 0.01 <= d < 1 %.3f; d < 0.01 %.3e when |d| >= 1e-20, else "0.00".
+ * FORMAT keys (calcVCFGenotypeKeys): every generic field non-null in some sample; GQ / DP if some
+ *   sample's value is not missing; AD / PL if some sample's array is non-null; FT if some sample has
+ *   it; written ascending, GT in front if some sample's GT array is non-null; an empty set with
+ *   n_sample > 0 is [GT]; n_sample == 0: no FORMAT column.  A key without a FORMAT line: HBAM_ERUNTIME.
+ * Per sample, header order: GT: encoded >> 1 is 0 for '.', else allele index + 1, outside [0,
+ *   n_allele]: HBAM_ERUNTIME; the separator is '|' when encoded[0] & 1, else '/'; GT among the keys
+ *   and this sample's array null: HBAM_ERUNTIME.  Then the other keys: DP, GQ decimal, missing '.', a
+ *   vector length other than 1: HBAM_EUNSUPPORTED; AD, PL joined by ',', null '.'; generic: the INFO
+ *   value text, and a null one prints '.' repeated Number times with ',' when Number is above 1
+ *   (Number A = n_allele - 1, R = n_allele, a fixed integer, '.' = 1).  Trailing values made only of
+ *   '.' and ',' are dropped from the sample's end; the survivors are joined by ':', after the GT when
+ *   it is a key.  A genotype block whose typed values run past l_indiv: HBAM_ETRIBBLE.
+ * Beyond the list (this library's choices where it is silent): a frame that runs past data_len, a
+ *   typed value that runs past l_shared, a sample count other than the header's or n_allele < 1:
+ *   HBAM_ETRIBBLE; CHROM outside the contigs, a dictionary offset outside the dictionary (FILTER, INFO
+ *   and FORMAT keys; keys are single integers), an ID or allele that is not a string, a GT / DP / GQ /
+ *   AD / PL field that is not of integer type, a second GT field, a typed value of an unknown type:
+ *   HBAM_ERUNTIME.  A generic FORMAT key stored twice is written twice, in field order.  A record is
+ *   checked in line order: the site left to right, the genotype fields' headers left to right, then
+ *   the samples.
+ * First failing record: it ends the output, as in hbam_sam_render: status, err_record = n_records =
+ *   its output position; text_len, line_off and deferred cover the lines before it.
+ *
+ * The device renders a float only where the text is provably the rule's.  QUAL: finite, sign bit
+ * clear, below 10^7, and 8q not an odd integer (there the %.2f tie meets the double round trip above).
+ * INFO floats: +0.0 / -0.0 "0.00"; 0.01 <= v < 1 %.3f; 1 <= v < 10^7 %.2f; both by exact integer
+ * arithmetic on mantissa and exponent, HALF_UP.  A record is DEFERRED when it has any other float; a
+ * FORMAT field of float or char type, or an FT; a null generic value under Number=G; a repeated INFO
+ * key (the host applies last-wins); or more INFO keys, FILTER entries, FORMAT fields or alleles per
+ * call than the HBAM_VCF_MAX_* caps.  A deferred record is checked like any other.
+ *
+ * Every length taken from a record is checked against l_shared or l_indiv and data_len before it is
+ * used: a malformed record gives a status, never a read outside the record and the slack or a write
+ * outside text.  Timing: total_ms, walk_ms = the sizes passes + scans, huffman_ms = the per-line write
+ * pass, resolve_ms = the per-wave write pass (records of HBAM_VCF_WAVE_SAMPLES samples or more),
+ * n_records, ubuf_bytes = the text bytes. */
+typedef hbam_sam_text hbam_vcf_text;
+int hbam_vcf_render(hbam_ctx* ctx, const uint8_t* data, uint64_t data_len, const uint64_t* rec_off,
+                    const uint32_t* perm, uint64_t n, int on_device, const hbam_bcf_header* hdr,
+                    const hbam_vcf_meta* meta, hbam_vcf_text* out);
+
 /* ---- FASTQ and QSEQ: FastqInputFormat / FastqRecordReader (FastqInputFormat.java:56-393) and
  * QseqInputFormat / QseqRecordReader (QseqInputFormat.java:58-429) over one FileSplit -------------
  * Both fill SequencedFragment values (SequencedFragment.java).  The line rule is the reference's own
