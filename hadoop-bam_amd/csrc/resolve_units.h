@@ -385,7 +385,11 @@ __global__ __launch_bounds__(64, RU_WAVES) void k_resolve_units(const BlockRec* 
       }
     }
     if ((tail0 & 0x80000000u) && (tail0 & 0xffffu) / RS_S == k && lane == 0) {
-      // final match shorter than 3 bytes (the output filled up inside it); last token
+      // final match shorter than 3 bytes (the output filled up inside it); last token.  Reached in
+      // production: the Huffman pass leaves its symbol loop on the cut match with exit code 2, but
+      // then op == isize, so the block's status is INF_OK (inflate_tok.h, `leave:`), as zlib fills
+      // the output and stops; a member whose CRC is that of those bytes is good
+      // (tests/test_lz77_gpu.py: test_member_cut_inside_its_last_match_resolves_the_tail)
       const uint32_t p = tail0 & 0xffffu, n = (tail0 >> 16) & 0x7fffu;
       uint32_t d = tails[2 * (uint64_t)b + 1];
       bool tail_bad = false;
