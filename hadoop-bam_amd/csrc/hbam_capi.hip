@@ -262,6 +262,18 @@ enum BufId {
   B_FT_LINEOFF,
   B_FT_SMALL,
   B_FT_TEXT,
+  // FASTA (hbam_fasta.hip)
+  B_FA_GT,
+  B_FA_CNT,
+  B_FA_OFF,
+  B_FA_SECT,
+  B_FA_SMALL,
+  B_FA_COLS,
+  B_FA_TREE,
+  B_FA_CAP,
+  B_FA_SCAN,
+  B_FA_KEY,
+  B_FA_SEQ,
   B_COUNT_ALL
 };
 
@@ -2748,5 +2760,6 @@ extern "C" int64_t hbam_bgzf_compress(hbam_ctx* c, const uint8_t* src, int src_o
 #include "hbam_sam.hip"
 #include "hbam_samtext.hip"
 #include "hbam_fastq.hip"
+#include "hbam_fasta.hip"
 #include "hbam_fragtext.hip"
 #include "hbam_vcftext.hip"

@@ -5,7 +5,8 @@ SAMRecordWritable, BAMSplitGuesser, util.BGZFSplitGuesser, util.BGZFBlockIndexer
 shuffle sort (cli/plugins/Sort) and its BAM output (BAMRecordWriter, KeyIgnoringBAMOutputFormat,
 util.SAMOutputPreparer, cli.Utils.mergeSAMInto) and its SAM text output (SAMRecordWriter,
 KeyIgnoringAnySAMOutputFormat, the View plugin), and the read formats FASTQ and QSEQ in both
-directions (FastqInputFormat, QseqInputFormat, FastqOutputFormat, QseqOutputFormat), and VCF text
+directions (FastqInputFormat, QseqInputFormat, FastqOutputFormat, QseqOutputFormat), FASTA input
+(FastaInputFormat, ReferenceFragment), and VCF text
 output over BCF records (VCFRecordWriter, KeyIgnoringVCFOutputFormat, vcf_sort); compute runs
 in libhbam.so (HIP, gfx950) through the C ABI of include/hbam.h.
 """
@@ -27,6 +28,7 @@ from .sam_text import (  # noqa: F401
 from .fastq import (  # noqa: F401
     FastqInputFormat, FastqRecordReader, FormatConstants, FormatException, NumberFormatException,
     QseqInputFormat, QseqRecordReader, SequencedFragment)
+from .fasta import FastaInputFormat, FastaRecordReader, ReferenceFragment  # noqa: F401
 from .fastq_text import (  # noqa: F401
     FastqOutputFormat, FastqRecordWriter, QseqOutputFormat, QseqRecordWriter, convert)
 from .vcf_text import (  # noqa: F401

@@ -71,6 +71,7 @@ EXPORTS = [
     "hbam_fastq_decode_split", "hbam_qseq_decode_split", "hbam_frag_columns_to_host", "hbam_frag_release",
     "hbam_frag_render",
     "hbam_bcf_header_text", "hbam_vcf_render",
+    "hbam_fasta_sections", "hbam_fasta_decode_split", "hbam_fasta_columns_to_host", "hbam_fasta_release",
 ]
 
 # hbam_read_fn: int64_t read(void* user, uint64_t offset, uint64_t len, uint8_t* dst)
@@ -204,6 +205,18 @@ class FragColumnsC(C.Structure):
                                           "key_off", "seq_off", "qual_off", "key", "seq", "qual")] + \
                [("key_len", C.c_uint64), ("seq_len", C.c_uint64), ("qual_len", C.c_uint64),
                 ("text_base", C.c_uint64)]
+
+
+class FastaColumnsC(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("status", C.c_int32), ("host", C.c_int32), ("err_pos", C.c_uint64),
+                ("first_pos", C.c_uint64), ("end_pos", C.c_uint64)] + \
+               [(k, C.c_void_p) for k in ("rec_off", "pos_after", "position", "line_len", "key_off", "seq_off",
+                                          "key", "seq")] + \
+               [("key_len", C.c_uint64), ("seq_len", C.c_uint64), ("index_off", C.c_uint32),
+                ("index_len", C.c_uint32), ("text_base", C.c_uint64)]
+
+
+FASTA_FIELDS = [("rec_off", np.uint64), ("pos_after", np.uint64), ("position", np.int32), ("line_len", np.uint32)]
 
 
 class FragTextC(C.Structure):
@@ -356,6 +369,12 @@ def load(path=None):
         "hbam_frag_release": (None, [vp, C.POINTER(FragColumnsC)]),
         "hbam_frag_render": (C.c_int, [vp, C.POINTER(FragColumnsC), vp, C.c_int, C.c_uint64, vp, C.c_uint64,
                                        C.c_int32, C.c_int32, C.c_uint32, C.POINTER(FragTextC)]),
+        "hbam_fasta_sections": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64, vp, C.c_uint64,
+                                          C.POINTER(C.c_uint64)]),
+        "hbam_fasta_decode_split": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+                                              C.c_uint64, C.POINTER(FastaColumnsC)]),
+        "hbam_fasta_columns_to_host": (C.c_int, [vp, C.POINTER(FastaColumnsC), C.POINTER(FastaColumnsC)]),
+        "hbam_fasta_release": (None, [vp, C.POINTER(FastaColumnsC)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name, None)
@@ -1136,6 +1155,56 @@ class Context:
             out[name + "_off"] = _host_array(getattr(h, name + "_off"), k + 1, np.uint64)
             out[name] = _host_array(getattr(h, name), int(getattr(h, name + "_len")), np.uint8)
         self.L.hbam_frag_release(self.h, C.byref(h))
+        out["timing"] = self.timing()
+        return out
+
+    # ---- FASTA (hbam_fasta.hip) --------------------------------------------------------------------
+    def fasta_sections(self, data, text_base=0):
+        """hbam_fasta_sections over one window -> {"rc", "offsets"}: the file offsets of every '>'
+        (uint64, ascending).  The size query and the call that fills the array."""
+        p, n, dev, keep = self._ptr(data)
+        cnt = C.c_uint64(0)
+        rc = self.L.hbam_fasta_sections(self.h, p, dev, int(text_base), n, None, 0, C.byref(cnt))
+        if rc not in (HBAM_OK, HBAM_EMORE):
+            return {"rc": rc, "error": self.last_error()}
+        out = np.zeros(int(cnt.value), np.uint64)
+        if rc == HBAM_EMORE:
+            rc = self.L.hbam_fasta_sections(self.h, p, dev, int(text_base), n, C.c_void_p(out.ctypes.data), len(out),
+                                            C.byref(cnt))
+            if rc:
+                return {"rc": rc, "error": self.last_error()}
+        return {"rc": 0, "offsets": out, "timing": self.timing()}
+
+    def fasta_decode_split_device(self, data, start, length, text_base=0, file_len=None):
+        """hbam_fasta_decode_split -> (rc, device FastaColumnsC)."""
+        p, n, dev, keep = self._ptr(data)
+        if file_len is None:
+            file_len = text_base + n
+        d = FastaColumnsC()
+        rc = self.L.hbam_fasta_decode_split(self.h, p, dev, int(text_base), n, int(file_len), int(start), int(length),
+                                            C.byref(d))
+        return rc, d
+
+    def fasta_decode_split(self, data, start, length, text_base=0, file_len=None):
+        """FastaRecordReader over one split -> host numpy columns: n, status, err_pos, first_pos,
+        end_pos, FASTA_FIELDS, index_off / index_len (the indexSequence inside the window) and the
+        pools key / seq with their n + 1 offsets."""
+        rc, d = self.fasta_decode_split_device(data, start, length, text_base, file_len)
+        if rc:
+            return {"rc": rc, "error": self.last_error()}
+        h = FastaColumnsC()
+        rc = self.L.hbam_fasta_columns_to_host(self.h, C.byref(d), C.byref(h))
+        if rc:
+            return {"rc": rc, "error": self.last_error()}
+        k = int(h.n)
+        out = {"rc": 0, "n": k, "status": int(h.status), "err_pos": int(h.err_pos), "first_pos": int(h.first_pos),
+               "end_pos": int(h.end_pos), "index_off": int(h.index_off), "index_len": int(h.index_len)}
+        for name, dt in FASTA_FIELDS:
+            out[name] = _host_array(getattr(h, name), k, dt)
+        for name in ("key", "seq"):
+            out[name + "_off"] = _host_array(getattr(h, name + "_off"), k + 1, np.uint64)
+            out[name] = _host_array(getattr(h, name), int(getattr(h, name + "_len")), np.uint8)
+        self.L.hbam_fasta_release(self.h, C.byref(h))
         out["timing"] = self.timing()
         return out
 

@@ -11,10 +11,10 @@ A .gz file is not splittable and is inflated here with zlib (one DEFLATE stream 
 parallelism, the BGZF kernels do not apply); its text goes through the same device call with
 start = 0 and an unbounded end.  Other codec extensions raise NotImplementedError.
 
-The output formats (FastqOutputFormat, QseqOutputFormat) are in fastq_text.py.  Out of scope: FASTA,
-SequencedFragment's Writable wire form (readFields / write) and a Java shim class.  Inputs the
-device path does not restate raise SeqUnsupportedException (include/hbam.h lists them under
-HBAM_EUNSUPPORTED).
+The output formats (FastqOutputFormat, QseqOutputFormat) are in fastq_text.py, FASTA input in
+fasta.py.  Out of scope: SequencedFragment's Writable wire form (readFields / write) and a Java shim
+class.  Inputs the device path does not restate raise SeqUnsupportedException (include/hbam.h lists
+them under HBAM_EUNSUPPORTED).
 """
 import zlib
 

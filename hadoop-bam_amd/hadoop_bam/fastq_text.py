@@ -24,7 +24,7 @@ so any gzip reader (GzipCodec, zlib, fastq.py's own reader) inflates the file to
 file's bytes are not GzipCodec's (one deflate stream from java.util.zip), which are out of scope,
 as are the other codecs.
 
-Out of scope: FASTA, SequencedFragment's Writable wire form.
+Out of scope: SequencedFragment's Writable wire form.
 """
 import os
 

@@ -1095,6 +1095,84 @@ int hbam_frag_render(hbam_ctx* ctx, const hbam_frag_columns* cols, const uint8_t
                      uint64_t window_len, const uint32_t* perm, uint64_t n, int32_t format, int32_t encoding,
                      uint32_t flags, hbam_frag_text* out);
 
+/* ---- FASTA: FastaInputFormat.getSplits (FastaInputFormat.java:59-144) and FastaRecordReader
+ * (:146-361) over one FileSplit, filling ReferenceFragment values (ReferenceFragment.java) ----------
+ * The line rule is LineReader.readLine's, as for FASTQ and QSEQ above.
+ *
+ * hbam_fasta_sections: the file offsets (text_base + the position in the window) of every byte '>'
+ * of text[0, text_len), ascending, into the host array out_off[cap]; *n = their count.  getSplits
+ * starts a section at every '>' wherever it stands in a line: with p0 < p1 < ... < pm over the whole
+ * file its splits are (p_i, p_{i+1} - 1 - p_i) and (p_m, file_len - p_m), and (0, file_len) without
+ * any.  text is host or device memory at any alignment under hbam_vcf_decode_split's window contract,
+ * at most 2 GiB (HBAM_EINVAL above).  cap too small: HBAM_EMORE, *n is the count and nothing is
+ * written (cap = 0 with out_off = NULL is the size query).  Timing: scan_ms the byte scan, walk_ms
+ * scan + scatter, total_ms, ubuf_bytes = text_len, n_records = *n. */
+int hbam_fasta_sections(hbam_ctx* ctx, const uint8_t* text, int on_device, uint64_t text_base, uint64_t text_len,
+                        uint64_t* out_off, uint64_t cap, uint64_t* n);
+
+/* Output of hbam_fasta_decode_split: device memory owned by the context, valid until its next
+ * hbam_fasta_decode_split (host = 0); after hbam_fasta_columns_to_host host arrays owned by the
+ * caller (host = 1), freed by hbam_fasta_release.  Record i's key is key[key_off[i], key_off[i + 1]),
+ * its sequence seq[seq_off[i], seq_off[i + 1]).  The indexSequence every record carries is the
+ * window's bytes [index_off, index_off + index_len), tabs kept. */
+typedef struct hbam_fasta_columns {
+  uint64_t n;          /* records returned before `status` */
+  int32_t status;      /* HBAM_OK, the exception the constructor (n = 0) or next() raises, or HBAM_EMORE */
+  int32_t host;
+  uint64_t err_pos;    /* HBAM_ERUNTIME: the file offset of the line the message names */
+  uint64_t first_pos;  /* getPos() before the first next(): the byte after the header line */
+  uint64_t end_pos;    /* getPos() after the next() that ends the split (returns false, or raises) */
+  uint64_t* rec_off;   /* file offset of the line's first byte */
+  uint64_t* pos_after; /* getPos() after the next() that returns this record */
+  int32_t* position;   /* ReferenceFragment.position */
+  uint32_t* line_len;  /* the line's own bytes: seq[seq_off[i], seq_off[i] + line_len[i]) is the clean line */
+  uint64_t* key_off;   /* u64[n + 1] */
+  uint64_t* seq_off;
+  uint8_t* key;
+  uint8_t* seq;
+  uint64_t key_len;    /* bytes in each pool */
+  uint64_t seq_len;
+  uint32_t index_off;  /* relative to the window's first byte (file offset text_base) */
+  uint32_t index_len;
+  uint64_t text_base;
+} hbam_fasta_columns;
+
+/* FastaRecordReader over FileSplit [start, start + length) of an uncompressed FASTA file of file_len
+ * bytes.  text = file bytes [text_base, text_base + text_len), a window of at most 2 GiB (HBAM_EINVAL
+ * above) with text_base <= start, under hbam_vcf_decode_split's alignment contract.  (A compressed
+ * file never reaches this call: its reader has no indexSequence and its first non-empty line raises
+ * NullPointerException, which the caller answers on the host.)
+ *
+ * Constructor (positionAtFirstRecord, :207-232): the line at `start` is read whole; its first
+ * min(20000, length) content bytes are stored.  indexSequence = the stored bytes without the first,
+ * which is dropped untested.  first_pos = start + the bytes the line consumes.  n = 0 and
+ *   HBAM_EINDEX        nothing stored (substring(1, 0)): length == 0, an empty line, the end of the file;
+ *   HBAM_EUNSUPPORTED  a stored byte >= 0x80 (Text.toString / String.getBytes are not restated).
+ * next (:322-339): every line that starts below start + length is a record, empty lines and later
+ * '>' lines included, and is read to its own end; the end of the file ends the split.  A line that
+ * consumes 20000 bytes or more is HBAM_ERUNTIME (err_pos = its start, end_pos = the byte behind
+ * it); the records before it stand.  position = 1 + (rec_off - first_pos) in Java int arithmetic:
+ * it counts bytes consumed, terminators included.  key = indexSequence + Integer.toString(position)
+ * with every '\t' as ':'.
+ * Sequence (scanFastaLine, :359) = line.getBytes() whole, the backing array of a Hadoop 1.2.1 Text
+ * that also held the header line and every earlier line: clear() keeps the array, append()
+ * reallocates to exactly the needed size only when it is too small (restated from upstream, unpinned).
+ * With L_-1 the stored header length ('>' included) and L_k the length of data line k, record k has
+ * cap_k = max(L_-1, L_0 .. L_k) bytes: byte c is the line's own for c < L_k, else byte c of line j,
+ * the largest j in [-1, k) with L_j > c.
+ * HBAM_EMORE: the window ends (before file_len) inside the header line or a line the reader reads;
+ * call again with a longer window.  HBAM_ENOMEM (returned): a pool does not fit device memory.
+ * Timing: scan_ms structural pass, walk_ms line starts and the header line, decode_ms the record
+ * pass, maxima and offsets, pools_ms the two pools, total_ms, ubuf_bytes = text_len, n_records,
+ * pool_bytes. */
+int hbam_fasta_decode_split(hbam_ctx* ctx, const uint8_t* text, int on_device, uint64_t text_base,
+                            uint64_t text_len, uint64_t file_len, uint64_t start, uint64_t length,
+                            hbam_fasta_columns* out);
+/* host copy of the n records' columns and the two pools */
+int hbam_fasta_columns_to_host(hbam_ctx* ctx, const hbam_fasta_columns* dev, hbam_fasta_columns* host);
+/* frees a host copy's arrays; clears the struct either way */
+void hbam_fasta_release(hbam_ctx* ctx, hbam_fasta_columns* cols);
+
 #ifdef __cplusplus
 }
 #endif
