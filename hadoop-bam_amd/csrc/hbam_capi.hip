@@ -274,6 +274,11 @@ enum BufId {
   B_FA_SCAN,
   B_FA_KEY,
   B_FA_SEQ,
+  // sparse chain build (build_chain_sparse)
+  B_SEG_CAND,
+  B_SEG_ENDS,
+  B_SEG_CNT,
+  B_SEG_POS,
   B_COUNT_ALL
 };
 
@@ -290,6 +295,13 @@ constexpr uint32_t MAX_SLICES = 16;
 // 5 GB 33.8 / 44.7, 10 GB 60 / 88.9 (profiles/r04/ab/huffman_wave_vs_lane_by_size.txt)
 // env HBAM_WAVE_MAX_BLOCKS overrides (tests, A/B)
 constexpr uint64_t WAVE_MAX_BLOCKS = 90000;
+// Sparse chain build: bytes per segment (one 64 KiB window scanned and one walker each), and the
+// smallest window that tries it: below, the walkers' serial hops cost more than the dense scan
+// of so few bytes.  env HBAM_CHAIN_SEG overrides the first and, unless HBAM_CHAIN_MIN is set
+// too, drops the second to 0 (tests: small files over many segments); HBAM_CHAIN_DENSE=1 forces
+// the dense path (tests, A/B).  Measurements: profiles/sparse_chain/ab.txt
+constexpr uint64_t CHAIN_SEG = 1ull << 20;
+constexpr uint64_t CHAIN_SPARSE_MIN = 256ull << 20;
 struct hbam_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -304,6 +316,12 @@ struct hbam_ctx {
   bool slices_forced = false;                     // ... and then applies to small calls too
   uint32_t tok_generic = 0;  // env HBAM_TOK_GENERIC=1: k_inflate_tokens' generic symbol loop only (tests, A/B)
   uint32_t tok_interior = 1;  // env HBAM_TOK_INTERIOR=0: its specialised loop without the interior body (tests, A/B)
+  uint64_t chain_seg = CHAIN_SEG;                // env HBAM_CHAIN_SEG
+  uint64_t chain_sparse_min = CHAIN_SPARSE_MIN;  // env HBAM_CHAIN_MIN
+  bool chain_dense = false;                      // env HBAM_CHAIN_DENSE=1
+  uint32_t chain_why = 0;           // SEGF_* flags of the last build_chain (0: none raised)
+  uint64_t chain_sparse_calls = 0;  // build_chain calls answered by the sparse form ...
+  uint64_t chain_dense_calls = 0;   // ... and by the dense path (hbam_chain_table reports both)
   hbam_timing timing{};
   uint64_t* pinned_small = nullptr;  // host pinned scalars
   uint64_t guess_batch = GUESS_BATCH;  // env HBAM_GUESS_BATCH overrides (tests: multi-batch)
@@ -418,9 +436,85 @@ struct Chain {
   uint64_t end_pos = 0;          // comp offset where the chain ends
 };
 
+// What reading a block at `pos`, where the chain stopped, raises.
+int32_t classify_chain_end(hbam_ctx* c, const uint8_t* dcomp, uint64_t comp_len, bool window_is_file_end,
+                           uint64_t pos) {
+  uint8_t hdr[32];
+  const uint64_t avail = comp_len - pos;
+  memset(hdr, 0, sizeof hdr);
+  const uint64_t nget = std::min<uint64_t>(avail, 32);
+  if (nget) {
+    if (copy_sync(c, hdr, dcomp + pos, nget, hipMemcpyDeviceToHost) != hipSuccess) return HBAM_EDEVICE;
+  }
+  if (avail == 0) return window_is_file_end ? HBAM_EEOF : HBAM_EMORE;
+  const uint32_t blen = nget >= 18 ? (uint32_t)rd16(hdr + 16) + 1u : 0u;
+  if (!window_is_file_end && (avail < 18 || blen > avail)) return HBAM_EMORE;
+  if (avail >= 18 && blen >= 18 && blen <= avail && blen > 32) {
+    // block header looks readable but was not accepted: classify with its footer
+    std::vector<uint8_t> full(blen + 8);
+    if (copy_sync(c, full.data(), dcomp + pos, blen, hipMemcpyDeviceToHost) != hipSuccess)
+      return HBAM_EDEVICE;
+    return readblock_error(full.data(), avail);
+  }
+  return readblock_error(hdr, avail);
+}
+
+// The sparse form of build_chain (kernels: hbam_kernels.hip, "K1, sparse form"): reads the first
+// 64 KiB of every segment and about 26 bytes per block instead of every compressed byte.
+// *took = 1 and the chain in ch / B_BLK when every walker stitched to its neighbour; *took = 0,
+// with why in c->chain_why, when the call has to go through the dense path.  Host round trips:
+// one for the flags, the block count and the chain's end, one in classify_chain_end (the dense
+// fast path: the candidate count, the flags and ends, classify_end).
+int build_chain_sparse(hbam_ctx* c, const uint8_t* dcomp, uint64_t comp_len, uint64_t start,
+                       bool window_is_file_end, Chain* ch, int* took) {
+  *took = 0;
+  const uint64_t span = comp_len - start, seg = c->chain_seg;
+  const uint64_t nseg = std::max<uint64_t>(1, span / seg);  // the last one: [seg, 2 seg) bytes
+  const uint32_t cap = (uint32_t)(seg / SEG_HOP_BYTES);
+  uint64_t *seg_cand, *seg_start, *seg_exit, *seg_base, *small;
+  uint32_t *seg_ncand, *seg_hops, *seg_pos;
+  BlockRec* blk;
+  int rc;
+  if ((rc = ensure(c, B_SEG_CAND, nseg * SEG_CANDS, &seg_cand))) return rc;
+  if ((rc = ensure(c, B_SEG_ENDS, 2 * nseg, &seg_start))) return rc;
+  if ((rc = ensure(c, B_SEG_CNT, 2 * nseg, &seg_ncand))) return rc;
+  if ((rc = ensure(c, B_SEG_POS, nseg * cap, &seg_pos))) return rc;
+  if ((rc = ensure(c, B_CHUNK_BASE, nseg + 1, &seg_base))) return rc;
+  if ((rc = ensure(c, B_SMALL, 16, &small))) return rc;
+  seg_exit = seg_start + nseg;
+  seg_hops = seg_ncand + nseg;
+  uint32_t* flags = (uint32_t*)small;
+  HIPCHK(c, hipMemsetAsync(small, 0, 16 * 8, c->stream));
+  if (nseg > 1)
+    k_seg_scan<<<(uint32_t)(nseg - 1), 256, 0, c->stream>>>(dcomp, start, comp_len, seg, seg_cand,
+                                                            seg_ncand, flags);
+  k_seg_walk<<<grid_for(nseg, 64), 64, 0, c->stream>>>(dcomp, start, comp_len, seg, nseg, seg_cand,
+                                                       seg_ncand, cap, seg_pos, seg_hops, seg_start,
+                                                       seg_exit, flags);
+  k_seg_stitch<<<1, 1024, 0, c->stream>>>(nseg, seg_hops, seg_start, seg_exit, seg_base, flags, small);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(c->pinned_small, small, 24, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->chain_why = ((uint32_t*)c->pinned_small)[0];
+  if (c->chain_why) return HBAM_OK;
+  const uint64_t nb = c->pinned_small[1];
+  if ((rc = ensure(c, B_BLK, nb + 1, &blk))) return rc;
+  k_seg_table<<<(uint32_t)nseg, 64, 0, c->stream>>>(dcomp, start, seg, cap, seg_pos, seg_hops, seg_base,
+                                                    blk);
+  HIPCHK(c, hipGetLastError());
+  ch->nb = nb;
+  ch->end_pos = c->pinned_small[2];
+  ch->end_code = classify_chain_end(c, dcomp, comp_len, window_is_file_end, ch->end_pos);
+  *took = 1;
+  return HBAM_OK;
+}
+
 // K1: block table of the chain starting at comp offset `start` (must be a block start).
 // Device-resident result in B_BLK (nb entries).  end_code: HBAM_EEOF for a clean end of
 // file, a readBlock error code, or HBAM_EMORE when the window ends mid-chain.
+// Windows of CHAIN_SPARSE_MIN bytes and more try the sparse form first; whatever it does not
+// accept (and every smaller window) takes the dense path below: every byte position tested
+// (k_scan_chunks), the candidates gathered and checked to be one chain (k_verify_chain).
 int build_chain(hbam_ctx* c, const uint8_t* dcomp, uint64_t comp_len, uint64_t start,
                 bool window_is_file_end, Chain* ch) {
   ch->nb = 0;
@@ -430,6 +524,17 @@ int build_chain(hbam_ctx* c, const uint8_t* dcomp, uint64_t comp_len, uint64_t s
     return HBAM_OK;
   }
   const uint64_t span = comp_len - start;
+  c->chain_why = 0;
+  if (!c->chain_dense && span >= c->chain_sparse_min) {
+    int took = 0, rc_s = build_chain_sparse(c, dcomp, comp_len, start, window_is_file_end, ch, &took);
+    if (rc_s) return rc_s;
+    if (took) {
+      ++c->chain_sparse_calls;
+      return HBAM_OK;
+    }
+    ch->nb = 0;
+  }
+  ++c->chain_dense_calls;
   const uint64_t nchunks = (span + SCAN_CHUNK - 1) / SCAN_CHUNK;
   uint32_t* chunk_cnt;
   uint64_t *chunk_base, *chunk_pos, *cand, *small;
@@ -497,25 +602,8 @@ int build_chain(hbam_ctx* c, const uint8_t* dcomp, uint64_t comp_len, uint64_t s
     first = c->pinned_small[8];
     memcpy(&last, c->pinned_small + 10, sizeof last);
   }
-  uint8_t hdr[32];
   auto classify_end = [&](uint64_t pos) -> int32_t {
-    const uint64_t avail = comp_len - pos;
-    memset(hdr, 0, sizeof hdr);
-    const uint64_t nget = std::min<uint64_t>(avail, 32);
-    if (nget) {
-      if (copy_sync(c, hdr, dcomp + pos, nget, hipMemcpyDeviceToHost) != hipSuccess) return HBAM_EDEVICE;
-    }
-    if (avail == 0) return window_is_file_end ? HBAM_EEOF : HBAM_EMORE;
-    const uint32_t blen = nget >= 18 ? (uint32_t)rd16(hdr + 16) + 1u : 0u;
-    if (!window_is_file_end && (avail < 18 || blen > avail)) return HBAM_EMORE;
-    if (avail >= 18 && blen >= 18 && blen <= avail && blen > 32) {
-      // block header looks readable but was not accepted: classify with its footer
-      std::vector<uint8_t> full(blen + 8);
-      if (copy_sync(c, full.data(), dcomp + pos, blen, hipMemcpyDeviceToHost) != hipSuccess)
-        return HBAM_EDEVICE;
-      return readblock_error(full.data(), avail);
-    }
-    return readblock_error(hdr, avail);
+    return classify_chain_end(c, dcomp, comp_len, window_is_file_end, pos);
   };
   if (first != start) {
     // the split's first block is not a BGZF block htsjdk accepts
@@ -710,6 +798,15 @@ hbam_ctx* hbam_create(int device_ordinal, const hbam_opts* opts) {
   if (const char* wm = getenv("HBAM_WAVE_MAX_BLOCKS")) c->wave_max_blocks = strtoull(wm, nullptr, 10);
   if (const char* tg = getenv("HBAM_TOK_GENERIC")) c->tok_generic = strtol(tg, nullptr, 10) != 0 ? 1u : 0u;
   if (const char* ti = getenv("HBAM_TOK_INTERIOR")) c->tok_interior = strtol(ti, nullptr, 10) != 0 ? 1u : 0u;
+  if (const char* sg = getenv("HBAM_CHAIN_SEG")) {
+    const unsigned long long v = strtoull(sg, nullptr, 10);
+    if (v > 0) {
+      c->chain_seg = std::min<uint64_t>(std::max<uint64_t>(v, SEG_MIN), 1ull << 30);
+      c->chain_sparse_min = 0;
+    }
+  }
+  if (const char* sm = getenv("HBAM_CHAIN_MIN")) c->chain_sparse_min = strtoull(sm, nullptr, 10);
+  if (const char* cd = getenv("HBAM_CHAIN_DENSE")) c->chain_dense = strtol(cd, nullptr, 10) != 0;
   if (const char* gb = getenv("HBAM_GUESS_BATCH")) {
     const long v = strtol(gb, nullptr, 10);
     if (v > 0) c->guess_batch = (uint64_t)v;
@@ -998,6 +1095,46 @@ int hbam_scan_blocks(hbam_ctx* c, const uint8_t* comp, int on_device, uint64_t l
   }
   return ch.end_code == HBAM_EEOF ? HBAM_OK : set_err(c, ch.end_code, "BGZF chain ends at %llu",
                                                       (unsigned long long)ch.end_pos);
+}
+
+int hbam_chain_table(hbam_ctx* c, const uint8_t* comp, int on_device, uint64_t len, uint64_t start,
+                     int window_is_file_end, hbam_block* out, uint64_t cap, hbam_chain_info* info) {
+  if (!c || !info) return HBAM_EINVAL;
+  if (!comp) {  // the context's counters and its last call's flags only
+    *info = hbam_chain_info{};
+    info->fallback_flags = c->chain_why;
+    info->sparse_calls = c->chain_sparse_calls;
+    info->dense_calls = c->chain_dense_calls;
+    return HBAM_OK;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint8_t* d;
+  int rc = stage_comp(c, comp, on_device, len, &d);
+  if (rc) return rc;
+  Chain ch;
+  const uint64_t sparse_before = c->chain_sparse_calls;
+  if ((rc = build_chain(c, d, len, start, window_is_file_end != 0, &ch))) return rc;
+  info->n_blocks = ch.nb;
+  info->end_pos = ch.end_pos;
+  info->end_code = ch.end_code;
+  info->sparse = c->chain_sparse_calls != sparse_before;
+  info->fallback_flags = c->chain_why;
+  info->pad = 0;
+  info->sparse_calls = c->chain_sparse_calls;
+  info->dense_calls = c->chain_dense_calls;
+  if (out && ch.nb) {
+    const uint64_t n = std::min(ch.nb, cap);
+    std::vector<BlockRec> hb(n);
+    HIPCHK(c, copy_sync(c, hb.data(), c->bufs[B_BLK].p, n * sizeof(BlockRec), hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < n; ++i) {
+      out[i].coff = hb[i].coff;
+      out[i].clen = hb[i].clen;
+      out[i].isize = hb[i].isize;
+      out[i].crc = hb[i].crc;
+      out[i].pad = 0;
+    }
+  }
+  return HBAM_OK;
 }
 
 int hbam_inflate(hbam_ctx* c, const uint8_t* comp, int on_device, uint64_t comp_len,

@@ -8,7 +8,20 @@ namespace hbam {
 
 constexpr uint32_t SCAN_CHUNK = 65536;  // bytes per scan workgroup (multiple of 256*16)
 constexpr uint32_t SCAN_CAP = 64;       // candidate slots per chunk
-constexpr uint32_t INFLATE_WG = 64;     // lanes (= blocks) per inflate workgroup
+// sparse chain build (k_seg_scan / k_seg_walk / k_seg_stitch / k_seg_table)
+constexpr uint32_t SEG_WINDOW = 65536;           // a BGZF block is at most 65,536 bytes
+constexpr uint32_t SEG_CANDS = 4;                // candidate slots per segment window
+constexpr uint64_t SEG_MIN = SEG_WINDOW + 64;    // smallest segment: the last window holds a whole header
+constexpr uint64_t SEG_HOP_BYTES = 2048;         // hop cap of a walker = SEG / this (9 x SEG / 18 KiB; the
+                                                 // last segment is up to 2 SEG long)
+enum : uint32_t {                                // why a call left the sparse path
+  SEGF_NOCAND = 1,   // a window without a candidate
+  SEGF_MANY = 2,     // a window with more than SEG_CANDS candidates
+  SEGF_DERAIL = 4,   // every candidate of a segment walked onto a bad header
+  SEGF_CAP = 8,      // a walker passed its hop cap
+  SEGF_STITCH = 16,  // a walker's exit is not the next segment's start
+};
+constexpr uint32_t INFLATE_WG = 64;    // lanes (= blocks) per inflate workgroup
 constexpr uint32_t LENS_SLOT = 352;     // per-block global scratch for code lengths
 constexpr uint32_t BITMAP_WORDS = 2048;  // per-block match-start bitmap (65536 bits)
 constexpr uint32_t WALK_CAP = 1880;     // >= 65536/35 record starts per block (BAM >= 36 B, BCF >= 35 B)

@@ -3,7 +3,9 @@
 // Stage map (SURVEY.md §2.1 build units -> reference hot loops):
 //   K1 k_scan_chunks/k_gather_cands/k_verify_chain  BGZF framing   [htsjdk] BCIS.readBlock header
 //                                                    parse; BGZFBlockIndexer.skipBlock :130-181
-//   K2 k_inflate                                     [htsjdk] BlockGunzipper.unzipBlock (zlib)
+//      k_seg_scan/k_seg_walk/k_seg_stitch/k_seg_table  the same table for large windows, without
+//                                                    the pass over every byte ("K1, sparse form")
+//   K2 k_inflate                                    [htsjdk] BlockGunzipper.unzipBlock (zlib)
 //      k_crc32                                       CRC32 check (BCIS.setCheckCrcs)
 //   K5 k_block_entry/k_block_walk/k_chain_fix/k_emit record boundaries: BAMRecordReader
 //                                                    .nextKeyValue loop :172-188 -> decode()
@@ -235,6 +237,184 @@ __global__ void k_verify_chain(const uint8_t* __restrict__ comp, const uint64_t*
   }
   blk[i] = r;
   if (!ok) atomicAdd(bad, 1u);
+}
+
+// ------------------------------------------------------------------------------------
+// K1, sparse form: the block table without a pass over the compressed bytes.  A BGZF block is at
+// most 65,536 bytes, so the first SEG_WINDOW bytes of any stretch of the chain hold a true block
+// start, and from a true start the chain follows by hops of BSIZE + 1.  The chain's window
+// [begin, end) is cut into nseg segments of `seg` bytes (the last one takes the remainder, so
+// it is at least `seg` long and its window holds a whole header):
+//   k_seg_scan   the candidates in each later segment's first SEG_WINDOW bytes (k_scan_chunks'
+//                predicate), at most SEG_CANDS, in position order
+//   k_seg_walk   one lane per segment hops from the segment's candidate (segment 0: from `begin`)
+//                to the next segment's begin, testing every header on the way
+//   k_seg_stitch segment w counts only if walker w-1 left the chain exactly on walker w's start:
+//                by induction from `begin` every start is then a true block boundary, and a
+//                header-shaped run inside a payload is never stitched to; exclusive scan of the
+//                hop counts
+//   k_seg_table  the BlockRec table in chain order
+// Anything unexpected raises a SEGF_* flag and the caller takes the dense path (k_scan_chunks).
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ bool bgzf_header_at(const uint8_t* __restrict__ comp, uint64_t p, uint64_t end) {
+  return p + 18 <= end && ld_u32_unaligned(comp + p) == 0x04088b1fu && ld_u16_unaligned(comp + p + 10) == 6u;
+}
+
+// grid: nseg - 1 workgroups of 256 (segment blockIdx.x + 1)
+__global__ __launch_bounds__(256) void k_seg_scan(const uint8_t* __restrict__ comp, uint64_t begin,
+                                                  uint64_t end, uint64_t seg,
+                                                  uint64_t* __restrict__ seg_cand,
+                                                  uint32_t* __restrict__ seg_ncand,
+                                                  uint32_t* __restrict__ flags) {
+  __shared__ uint32_t s_cnt;
+  __shared__ uint64_t s_pos[SEG_CANDS];
+  const uint64_t w = (uint64_t)blockIdx.x + 1;
+  const uint64_t b = begin + w * seg;
+  if (threadIdx.x == 0) s_cnt = 0;
+  __syncthreads();
+  for (uint32_t step = 0; step < SEG_WINDOW / (256 * 16); ++step) {
+    const uint64_t p0 = b + ((uint64_t)step * 256 + threadIdx.x) * 16;
+    if (p0 >= end) break;
+    uint32_t mask = scan_mask16(comp, p0, end);
+    while (mask) {
+      const uint32_t k = __ffs(mask) - 1u;
+      mask &= mask - 1u;
+      const uint32_t i = atomicAdd(&s_cnt, 1u);
+      if (i < SEG_CANDS) s_pos[i] = p0 + k;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t n = s_cnt;
+    if (n == 0) atomicOr(flags, SEGF_NOCAND);
+    if (n > SEG_CANDS) {  // which SEG_CANDS of them reached the slots is arbitrary: none is used
+      atomicOr(flags, SEGF_MANY);
+      n = 0;
+    }
+    for (uint32_t i = 1; i < n; ++i) {
+      const uint64_t v = s_pos[i];
+      uint32_t j = i;
+      while (j > 0 && s_pos[j - 1] > v) { s_pos[j] = s_pos[j - 1]; --j; }
+      s_pos[j] = v;
+    }
+    seg_ncand[w] = n;
+    for (uint32_t i = 0; i < n; ++i) seg_cand[w * SEG_CANDS + i] = s_pos[i];
+  }
+}
+
+// One lane per segment.  A walk ends well when it reaches the next segment's begin, or, in the
+// last segment, where the dense path's chain ends well: fewer than 18 bytes left, or a block
+// with a good header that runs past `end` (not counted).  A landing position that fails the
+// header test, or a block of fewer than 18 bytes, derails the walk, which starts again from the
+// window's next candidate; positions are kept relative to the segment's begin.
+__global__ __launch_bounds__(64) void k_seg_walk(const uint8_t* __restrict__ comp, uint64_t begin,
+                                                 uint64_t end, uint64_t seg, uint64_t nseg,
+                                                 const uint64_t* __restrict__ seg_cand,
+                                                 const uint32_t* __restrict__ seg_ncand, uint32_t cap,
+                                                 uint32_t* __restrict__ seg_pos,
+                                                 uint32_t* __restrict__ seg_hops,
+                                                 uint64_t* __restrict__ seg_start,
+                                                 uint64_t* __restrict__ seg_exit,
+                                                 uint32_t* __restrict__ flags) {
+  const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= nseg) return;
+  const uint64_t b = begin + w * seg;
+  const uint64_t stop = w + 1 < nseg ? b + seg : ~0ULL;
+  const uint32_t nc = w == 0 ? 1u : seg_ncand[w];
+  uint32_t* pos = seg_pos + w * cap;
+  uint32_t why = nc ? SEGF_DERAIL : 0u;  // (no candidate: k_seg_scan raised the flag)
+  for (uint32_t ci = 0; ci < nc; ++ci) {
+    const uint64_t p_first = w == 0 ? begin : seg_cand[w * SEG_CANDS + ci];
+    uint64_t p = p_first;
+    uint32_t n = 0;
+    bool ok = true;
+    while (p < stop) {
+      if (p + 18 > end) break;
+      if (!bgzf_header_at(comp, p, end)) { ok = false; break; }
+      const uint32_t bl = (uint32_t)ld_u16_unaligned(comp + p + 16) + 1u;
+      if (bl < 18) { ok = false; break; }
+      if (p + bl > end) break;
+      if (n >= cap) { ok = false; why = SEGF_CAP; break; }
+      pos[n++] = (uint32_t)(p - b);
+      p += bl;
+    }
+    if (ok) {
+      seg_hops[w] = n;
+      seg_start[w] = p_first;
+      seg_exit[w] = p;
+      return;
+    }
+    if (why == SEGF_CAP) break;
+  }
+  if (why) atomicOr(flags, why);
+  seg_hops[w] = 0;
+  seg_start[w] = ~0ULL - 1;  // matches no exit
+  seg_exit[w] = ~0ULL;
+}
+
+// One workgroup: the stitch test and the exclusive scan of the hop counts (seg_base[nseg] and
+// out[1] = blocks of the chain, out[2] = where it ends).
+__global__ __launch_bounds__(1024) void k_seg_stitch(uint64_t nseg, const uint32_t* __restrict__ seg_hops,
+                                                     const uint64_t* __restrict__ seg_start,
+                                                     const uint64_t* __restrict__ seg_exit,
+                                                     uint64_t* __restrict__ seg_base,
+                                                     uint32_t* __restrict__ flags, uint64_t* __restrict__ out) {
+  __shared__ uint32_t s_wsum[16];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  uint64_t run = 0;
+  bool mismatch = false;
+  for (uint64_t i0 = 0; i0 < nseg; i0 += 1024) {
+    const uint64_t i = i0 + threadIdx.x;
+    const uint32_t v = i < nseg ? seg_hops[i] : 0u;
+    if (i > 0 && i < nseg && seg_exit[i - 1] != seg_start[i]) mismatch = true;
+    uint32_t incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const uint32_t t = __shfl_up(incl, off);
+      if ((int)lane >= off) incl += t;
+    }
+    if (lane == 63) s_wsum[wv] = incl;
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 16; ++j) {
+      before += j < wv ? s_wsum[j] : 0u;
+      total += s_wsum[j];
+    }
+    if (i < nseg) seg_base[i] = run + before + incl - v;
+    run += total;
+    __syncthreads();
+  }
+  if (mismatch) atomicOr(flags, SEGF_STITCH);
+  if (threadIdx.x == 0) {
+    seg_base[nseg] = run;
+    out[1] = run;
+    out[2] = seg_exit[nseg - 1];
+  }
+}
+
+// One wave per segment: its blocks' records at seg_base[w] (every position passed the walker's
+// tests, so the footer lies inside [begin, end)).
+__global__ __launch_bounds__(64) void k_seg_table(const uint8_t* __restrict__ comp, uint64_t begin,
+                                                  uint64_t seg, uint32_t cap,
+                                                  const uint32_t* __restrict__ seg_pos,
+                                                  const uint32_t* __restrict__ seg_hops,
+                                                  const uint64_t* __restrict__ seg_base,
+                                                  BlockRec* __restrict__ blk) {
+  const uint64_t w = blockIdx.x;
+  const uint32_t n = seg_hops[w];
+  const uint64_t b = begin + w * seg, o = seg_base[w];
+  for (uint32_t i = threadIdx.x; i < n; i += 64) {
+    const uint64_t p = b + seg_pos[w * cap + i];
+    const uint32_t bl = (uint32_t)ld_u16_unaligned(comp + p + 16) + 1u;
+    BlockRec r;
+    r.coff = p;
+    r.clen = bl;
+    r.isize = ld_u32_unaligned(comp + p + bl - 4);
+    r.crc = ld_u32_unaligned(comp + p + bl - 8);
+    r.pad = 0;
+    blk[o + i] = r;
+  }
 }
 
 // ------------------------------------------------------------------------------------

@@ -72,6 +72,7 @@ EXPORTS = [
     "hbam_frag_render",
     "hbam_bcf_header_text", "hbam_vcf_render",
     "hbam_fasta_sections", "hbam_fasta_decode_split", "hbam_fasta_columns_to_host", "hbam_fasta_release",
+    "hbam_chain_table",
 ]
 
 # hbam_read_fn: int64_t read(void* user, uint64_t offset, uint64_t len, uint8_t* dst)
@@ -95,6 +96,12 @@ class Header(C.Structure):
 class Block(C.Structure):
     _fields_ = [("coff", C.c_uint64), ("clen", C.c_uint32), ("isize", C.c_uint32),
                 ("crc", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class ChainInfo(C.Structure):
+    _fields_ = [("n_blocks", C.c_uint64), ("end_pos", C.c_uint64), ("end_code", C.c_int32),
+                ("sparse", C.c_int32), ("fallback_flags", C.c_uint32), ("pad", C.c_uint32),
+                ("sparse_calls", C.c_uint64), ("dense_calls", C.c_uint64)]
 
 
 class Timing(C.Structure):
@@ -274,6 +281,8 @@ def load(path=None):
         "hbam_parse_header": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.POINTER(Header)]),
         "hbam_scan_blocks": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64,
                                        C.POINTER(Block), C.c_uint64, C.POINTER(C.c_uint64)]),
+        "hbam_chain_table": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_int,
+                                       C.POINTER(Block), C.c_uint64, C.POINTER(ChainInfo)]),
         "hbam_inflate": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.POINTER(Block), C.c_uint64,
                                    C.c_int, vp, C.c_uint64, vp, vp]),
         "hbam_decode_split": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
@@ -575,6 +584,39 @@ class Context:
                    isize=np.array([arr[i].isize for i in range(k)], np.uint32),
                    crc=np.array([arr[i].crc for i in range(k)], np.uint32))
         return rc, out
+
+    def chain_table(self, data, start=0, window_is_file_end=True):
+        """hbam_chain_table: the block table of the chain from `start` of the window `data`, as
+        the decoders build it -> dict(coff, clen, isize, crc, nb, end_pos, end_code, sparse,
+        fallback_flags, sparse_calls, dense_calls)."""
+        p, n, dev, keep = self._ptr(data)
+        info = ChainInfo()
+        cap = n // 18 + 2
+        if cap > 1 << 20:  # a large window: count first (a second chain build) instead of n / 18 rows
+            rc = self.L.hbam_chain_table(self.h, p, dev, n, int(start), int(bool(window_is_file_end)),
+                                         None, 0, C.byref(info))
+            if rc:
+                raise RuntimeError("hbam_chain_table failed (%d): %s" % (rc, self.last_error()))
+            cap = int(info.n_blocks) + 1
+        arr = np.zeros(cap, np.dtype([("coff", "<u8"), ("clen", "<u4"), ("isize", "<u4"),
+                                      ("crc", "<u4"), ("pad", "<u4")]))
+        rc = self.L.hbam_chain_table(self.h, p, dev, n, int(start), int(bool(window_is_file_end)),
+                                     C.cast(C.c_void_p(arr.ctypes.data), C.POINTER(Block)), cap,
+                                     C.byref(info))
+        if rc:
+            raise RuntimeError("hbam_chain_table failed (%d): %s" % (rc, self.last_error()))
+        k = int(info.n_blocks)
+        out = {f: arr[f][:k].copy() for f in ("coff", "clen", "isize", "crc")}
+        out.update(nb=k, end_pos=int(info.end_pos), end_code=int(info.end_code), sparse=int(info.sparse),
+                   fallback_flags=int(info.fallback_flags), sparse_calls=int(info.sparse_calls),
+                   dense_calls=int(info.dense_calls))
+        return out
+
+    def chain_counters(self):
+        """(sparse, dense) chain builds of this context so far, by every entry point."""
+        info = ChainInfo()
+        self.L.hbam_chain_table(self.h, None, 0, 0, 0, 1, None, 0, C.byref(info))
+        return int(info.sparse_calls), int(info.dense_calls)
 
     def inflate(self, data, blocks, check_crc=True):
         p, n, dev, keep = self._ptr(data)

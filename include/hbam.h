@@ -174,6 +174,28 @@ int hbam_parse_header(hbam_ctx* ctx, const uint8_t* file, int on_device, uint64_
 int hbam_scan_blocks(hbam_ctx* ctx, const uint8_t* comp, int on_device, uint64_t len,
                      uint64_t base_off, hbam_block* out, uint64_t cap, uint64_t* n_out);
 
+/* The block table every decode builds first: the chain from offset `start` of the window
+ * comp[0, len), block offsets relative to `comp`, at most `cap` of them copied to `out` (may be
+ * NULL).  end_pos is where the chain stops and end_code what reading a block there raises
+ * (HBAM_EEOF: clean end of file; HBAM_EMORE: the window ends mid-chain and is not the file's
+ * end).  Windows of 256 MiB and more are built by the sparse form (one 64 KiB scan window and
+ * one chain walker per segment; env HBAM_CHAIN_SEG = segment bytes, which also admits every
+ * size; HBAM_CHAIN_MIN = smallest window in bytes); whatever it does not accept, smaller windows,
+ * and everything under env HBAM_CHAIN_DENSE=1 goes through the dense scan of every byte
+ * position.  The three are read when the context is created.  sparse = 1 when the sparse form
+ * answered this call; fallback_flags = why it did not (bit 0 a scan window without a candidate,
+ * 1 with more than 4, 2 every candidate of a segment derailed, 3 hop cap, 4 stitch mismatch; 0
+ * when it was not tried).  sparse_calls / dense_calls count the context's chain builds so
+ * far, by all entry points.  comp = NULL: the counters and the last build's flags only. */
+typedef struct hbam_chain_info {
+  uint64_t n_blocks, end_pos;
+  int32_t end_code, sparse;
+  uint32_t fallback_flags, pad;
+  uint64_t sparse_calls, dense_calls;
+} hbam_chain_info;
+int hbam_chain_table(hbam_ctx* ctx, const uint8_t* comp, int on_device, uint64_t len, uint64_t start,
+                     int window_is_file_end, hbam_block* out, uint64_t cap, hbam_chain_info* info);
+
 /* ---- batched inflate: [htsjdk] BlockGunzipper.unzipBlock (JDK zlib).  Blocks are
  * relative to `comp`; output concatenated into host `out` at out_off (n+1 entries,
  * exclusive scan of ISIZE, filled by the call).  blk_status: 0, HBAM_EFORMAT (short

@@ -44,4 +44,6 @@ for kw in cases:
     bad_total += bad
     print("case %-40s blocks %7d U %.3f GB rc %d crc/status mismatches %d"
           % (kw, n, off[-1] / 1e9, rc, bad), flush=True)
+if hasattr(ctx.L, "hbam_chain_table"):
+    print("block tables: %d by the sparse chain build, %d by the dense path" % ctx.chain_counters(), flush=True)
 sys.exit(1 if bad_total else 0)
