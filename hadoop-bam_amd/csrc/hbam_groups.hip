@@ -13,7 +13,11 @@
 // BinaryTagCodec.getIntegerType, the odd-length sequence's pad nibble zeroed, absent qualities
 // written as 0xFF — and the bin written as 0 for an unplaced record; a replaced tag keeps its
 // place in the attribute list, a removed one leaves it (the FixMate encoder's rule,
-// hbam_consumers.hip).  One thread per record: length pass, exclusive scan, write pass.
+// hbam_consumers.hip).  getAttribute decodes the whole variable block, so with either step on a
+// record whose n_cigar / l_seq claim more than its block_size holds (or whose block_size is under
+// the 32 fixed bytes) raises SAMFormatException, tag or no tag: grp_encode's layout check, which
+// oracle.rewrite_group_tags makes too (tests/merge_cases.py holds both to it).  One thread per
+// record: length pass, exclusive scan, write pass.
 #pragma once
 
 namespace hbam {

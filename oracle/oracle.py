@@ -523,11 +523,13 @@ def merged_dictionary(dicts):
 def correct_payloads(pay, off, keys, ref_map):
     """Utils.correctSAMRecordForMerging + SortRecordReader's re-key on SAMRecordWritable
     payloads (copy): refID -> ref_map, next refID too for paired reads, the coordinate key
-    recomputed where refID changed.  -> (payload, keys, first record raising or -1)."""
+    recomputed where refID changed.  An unpaired read's mate refID is never looked at
+    (setMateReferenceIndex runs under getReadPairedFlag only, cli/Utils.java:301): whatever it
+    holds stays and refuses nothing.  -> (payload, keys, first record raising or -1)."""
     import struct
     pay = np.array(pay, np.uint8, copy=True)
     keys = np.array(keys, np.int64, copy=True)
-    n_in = len(ref_map)
+    n_in = 0 if ref_map is None else len(ref_map)
     for i in range(len(off) - 1):
         o = int(off[i])
         ref, pos = struct.unpack_from("<ii", pay, o + 4)
@@ -538,11 +540,12 @@ def correct_payloads(pay, off, keys, ref_map):
             return -1 if x == -1 else (int(ref_map[x]) if 0 <= x < n_in else n_in)
         nr = tr(ref)
         nm = tr(mref) if flag & 1 else mref
-        if nr >= n_in or nm >= n_in:
+        if nr >= n_in or (flag & 1 and nm >= n_in):
             return pay, keys, i
         if nr != ref:
             struct.pack_into("<i", pay, o + 4, nr)
-            if not (flag & 4) and nr >= 0 and np.int32(pos + 1) >= 0:
+            # getAlignmentStart() = pos + 1 in Java int arithmetic: Integer.MAX_VALUE wraps below 0
+            if not (flag & 4) and nr >= 0 and ((pos + 1 + 2**31) % 2**32) - 2**31 >= 0:
                 keys[i] = (nr << 32) | pos  # getKey0: the int pos sign-extended before the OR
         if nm != mref:
             struct.pack_into("<i", pay, o + 24, nm)
@@ -710,9 +713,19 @@ def rewrite_group_tags(pay, off, groups, inp):
     SAMRecordWritable payloads, and BAMRecordCodec.encode of every record on which setAttribute ran
     (htsjdk 1.131 restated, parity unpinned: integers re-typed, pad nibble 0, absent qualities
     0xFF, bin 0 when unplaced; a replaced tag keeps its place).  -> (payload, offsets); raises
-    GroupRewriteError(kind, record) where the reference's map task fails."""
+    GroupRewriteError(kind, record) where the reference's map task fails.
+
+    getAttribute decodes the whole variable block, so with either step on, a record whose
+    n_cigar / l_seq claim more than its block_size holds (or whose block_size is under the 32
+    fixed bytes) raises SAMFormatException whether or not it carries a tag: the layout check
+    hbam_rewrite_groups makes (htsjdk restated, parity unpinned).
+
+    groups["rg_lookup"], where present, is the per-input table RG values are looked up in; the
+    reference uses the program-group table for RG too, which is the default.  hbam_rewrite_groups'
+    table format holds one table per tag, and the crafted cases fill the two differently."""
     import struct
-    pg_map = groups["pg"].get(inp)  # the RG lookup uses the PROGRAM-group table too (:322)
+    # the RG lookup uses the PROGRAM-group table too (:322)
+    maps = {b"PG": groups["pg"].get(inp), b"RG": groups.get("rg_lookup", groups["pg"]).get(inp)}
     todo = [t for t, c in ((b"PG", groups["pg_collisions"]), (b"RG", groups["rg_collisions"])) if c]
     out = []
     for i in range(len(off) - 1):
@@ -720,9 +733,13 @@ def rewrite_group_tags(pay, off, groups, inp):
         if not todo:
             out.append(r)
             continue
+        if len(r) < 36:
+            raise GroupRewriteError("SAMFormatException", i)
         lrn, nc, ls = r[12], struct.unpack_from("<H", r, 16)[0], max(0, struct.unpack_from("<i", r, 20)[0])
         head = 36 + lrn + 4 * nc
         vstart = head + (ls + 1) // 2 + ls
+        if vstart > len(r):
+            raise GroupRewriteError("SAMFormatException", i)
         try:
             items = _aux_items(r[vstart:])
         except ValueError:
@@ -734,9 +751,9 @@ def rewrite_group_tags(pay, off, groups, inp):
                 continue
             if items[first][1] != b"Z":
                 raise GroupRewriteError("ClassCastException", i)
-            if pg_map is None:
+            if maps[t] is None:
                 raise GroupRewriteError("NullPointerException", i)
-            edits[first] = pg_map.get(items[first][2][:-1])
+            edits[first] = maps[t].get(items[first][2][:-1])
         if not edits:
             out.append(r)
             continue

@@ -20,13 +20,35 @@ def aux_z(tag, s):
     return tag.encode() + b"Z" + s.encode() + b"\0"
 
 
+def aux_a(tag, ch):
+    return tag.encode() + b"A" + ch
+
+
+def aux_f(tag, x):
+    return tag.encode() + b"f" + struct.pack("<f", x)
+
+
+def aux_h(tag, hexdigits):
+    return tag.encode() + b"H" + hexdigits + b"\0"
+
+
+def aux_b(tag, sub, values):
+    fmt = {"c": "b", "C": "B", "s": "h", "S": "H", "i": "i", "I": "I", "f": "f"}[sub]
+    return tag.encode() + b"B" + sub.encode() + struct.pack("<I", len(values)) + struct.pack("<%d%s" % (len(values), fmt), *values)
+
+
 def record(name=b"r", flag=0, ref=0, pos=0, mapq=60, cigar=((10, 0),), l_seq=10, aux=b"",
-           nref=-1, npos=-1, tlen=0, bin_=4681, qual_absent=False, seed=0, raw_ops=None):
-    """One payload.  cigar: (len, op) pairs; raw_ops: u32 CIGAR words as given (garbage ops)."""
+           nref=-1, npos=-1, tlen=0, bin_=4681, qual_absent=False, seed=0, raw_ops=None, seq=None, qual=None):
+    """One payload.  cigar: (len, op) pairs; raw_ops: u32 CIGAR words as given (garbage ops);
+    seq: the packed sequence bytes as given (the pad nibble of an odd l_seq included); qual: the
+    quality bytes as given."""
     rng = np.random.default_rng(seed)
     words = list(raw_ops) if raw_ops is not None else [(ln << 4) | op for ln, op in cigar]
-    seq = bytes(rng.integers(0, 256, (l_seq + 1) // 2, dtype=np.uint8))
-    qual = b"\xff" * l_seq if qual_absent else bytes(rng.integers(0, 42, l_seq, dtype=np.uint8))
+    rnd_seq = bytes(rng.integers(0, 256, (l_seq + 1) // 2, dtype=np.uint8))
+    rnd_qual = b"\xff" * l_seq if qual_absent else bytes(rng.integers(0, 42, l_seq, dtype=np.uint8))
+    seq = rnd_seq if seq is None else bytes(seq)
+    qual = rnd_qual if qual is None else bytes(qual)
+    assert len(seq) == (l_seq + 1) // 2 and len(qual) == l_seq
     var = name + b"\0" + b"".join(struct.pack("<I", w) for w in words) + seq + qual + aux
     fixed = struct.pack("<iiBBHHHiiii", ref, pos, len(name) + 1, mapq, bin_, len(words), flag, l_seq,
                         nref, npos, tlen)
