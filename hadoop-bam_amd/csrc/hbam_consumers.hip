@@ -37,6 +37,7 @@ __device__ __forceinline__ void f4_st16(uint8_t* p, uint16_t v) {
   p[1] = (uint8_t)(v >> 8);
 }
 __device__ __forceinline__ int32_t f4_iadd(int32_t a, int32_t b) { return (int32_t)((uint32_t)a + (uint32_t)b); }
+__device__ __forceinline__ int32_t f4_ineg(int32_t a) { return (int32_t)(0u - (uint32_t)a); }  // -Integer.MIN_VALUE is itself
 __device__ __forceinline__ int64_t f4_key0(int32_t ref, int32_t s0) {  // BAMRecordReader.getKey0 :104-106
   return (int64_t)((uint64_t)(int64_t)ref << 32) | (int64_t)s0;
 }
@@ -367,10 +368,10 @@ __device__ void f4_set_mate_info(F4Rec& a, F4Rec& b) {  // SamPairUtil.setMateIn
   if (!f4_unm(a) && !f4_unm(b) && a.ref == b.ref) {
     const int32_t p1 = f4_neg(a) ? f4_end(a) : f4_start(a);
     const int32_t p2 = f4_neg(b) ? f4_end(b) : f4_start(b);
-    is = f4_iadd(f4_iadd(p2, -p1), p2 >= p1 ? 1 : -1);
+    is = f4_iadd(f4_iadd(p2, f4_ineg(p1)), p2 >= p1 ? 1 : -1);
   }
   a.tlen = is;
-  b.tlen = f4_iadd(0, -is);
+  b.tlen = f4_ineg(is);
 }
 __device__ __forceinline__ char f4_int_type(int64_t v) {  // BinaryTagCodec.getIntegerType
   if (v > 2147483647LL) return 'I';

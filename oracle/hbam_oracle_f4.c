@@ -69,6 +69,7 @@ static int layout_ok(const uint8_t* r) {
 /* ---- Summarize (cli/plugins/chipster/Summarize.java:664-755) ---------------------------- */
 /* Java int arithmetic (wraps) */
 static int32_t iadd(int32_t a, int32_t b) { return (int32_t)((uint32_t)a + (uint32_t)b); }
+static int32_t ineg(int32_t a) { return (int32_t)(0u - (uint32_t)a); } /* -Integer.MIN_VALUE is itself */
 
 /* SummarizeRecordReader.nextKeyValue over the records of one split.  split_status: the
  * exception the base BAMRecordReader raises after the n records (OR_OK when none).  Returns
@@ -248,7 +249,7 @@ static int32_t insert_size(const fm_rec* a, const fm_rec* b) {
   if (a->ref != b->ref) return 0; /* getReferenceName().equals */
   const int32_t p1 = fm_neg(a) ? fm_end(a) : fm_start(a);
   const int32_t p2 = fm_neg(b) ? fm_end(b) : fm_start(b);
-  return iadd(iadd(p2, -p1), p2 >= p1 ? 1 : -1);
+  return iadd(iadd(p2, ineg(p1)), p2 >= p1 ? 1 : -1);
 }
 /* SamPairUtil.setMateInfo(rec1, rec2, header) = setMateInfo(rec1, rec2, header, false) */
 static void set_mate_info(fm_rec* a, fm_rec* b) {
@@ -294,7 +295,7 @@ static void set_mate_info(fm_rec* a, fm_rec* b) {
   a->modified = b->modified = 1;
   const int32_t is = insert_size(a, b);
   a->tlen = is;
-  b->tlen = iadd(0, -is);
+  b->tlen = ineg(is);
 }
 
 /* BinaryTagCodec.getIntegerType */

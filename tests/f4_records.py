@@ -186,3 +186,14 @@ def fixmate_records(seed=5):
         R.append(record(b"", flag=1 | (0x40 if j == 0 else 0x80), ref=0, pos=10 * j, seed=9000 + j))
     order = rng.permutation(len(R))  # the shuffle sees them in any input order
     return [R[i] for i in order]
+
+
+def record_l0(**kw):
+    """A record whose l_read_name is 0: no name and no terminating NUL, the CIGAR directly behind
+    the fixed fields.  getReadName gives the empty name, as for l_read_name 1."""
+    b = bytearray(record(b"", **kw))
+    assert b[12] == 1 and b[36] == 0
+    del b[36]
+    b[12] = 0
+    struct.pack_into("<i", b, 0, len(b) - 4)
+    return bytes(b)
