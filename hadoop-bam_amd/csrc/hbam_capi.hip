@@ -279,6 +279,39 @@ enum BufId {
   B_SEG_ENDS,
   B_SEG_CNT,
   B_SEG_POS,
+  // summarize reduce / SummarySort (hbam_summary.hip)
+  B_SM_FIRST,
+  B_SM_TOFF,
+  B_SM_LEVELS,
+  B_SM_SKEY,
+  B_SM_PERM,
+  B_SM_ISF,
+  B_SM_HEAD,
+  B_SM_POSF,
+  B_SM_SEGP,
+  B_SM_CBEG,
+  B_SM_CEND,
+  B_SM_SB,
+  B_SM_SRID,
+  B_SM_PBEG,
+  B_SM_PEND,
+  B_SM_GC,
+  B_SM_GBASE,
+  B_SM_COLS,
+  B_SM_COLS2,
+  B_SM_LKEY,
+  B_SM_LPERM,
+  B_SM_LLEN,
+  B_SM_LOFF,
+  B_SM_TEXT,
+  B_SM_KSTART,
+  B_SM_KLEN,
+  B_SM_KKEY,
+  B_SM_KST,
+  B_SM_KBAD,
+  B_SM_KBEFORE,
+  B_SM_KSMALL,
+  B_SM_GLEN,
   B_COUNT_ALL
 };
 
@@ -2900,3 +2933,4 @@ extern "C" int64_t hbam_bgzf_compress(hbam_ctx* c, const uint8_t* src, int src_o
 #include "hbam_fasta.hip"
 #include "hbam_fragtext.hip"
 #include "hbam_vcftext.hip"
+#include "hbam_summary.hip"

@@ -7,7 +7,8 @@ util.SAMOutputPreparer, cli.Utils.mergeSAMInto) and its SAM text output (SAMReco
 KeyIgnoringAnySAMOutputFormat, the View plugin), and the read formats FASTQ and QSEQ in both
 directions (FastqInputFormat, QseqInputFormat, FastqOutputFormat, QseqOutputFormat), FASTA input
 (FastaInputFormat, ReferenceFragment), and VCF text
-output over BCF records (VCFRecordWriter, KeyIgnoringVCFOutputFormat, vcf_sort); compute runs
+output over BCF records (VCFRecordWriter, KeyIgnoringVCFOutputFormat, vcf_sort), and the summarize
+and summarysort plugins (cli/plugins/chipster: SummarizeReducer, SummarizeOutputFormat); compute runs
 in libhbam.so (HIP, gfx950) through the C ABI of include/hbam.h.
 """
 from ._lib import Context, HbamUnavailable, load  # noqa: F401
@@ -31,6 +32,8 @@ from .fastq import (  # noqa: F401
 from .fasta import FastaInputFormat, FastaRecordReader, ReferenceFragment  # noqa: F401
 from .fastq_text import (  # noqa: F401
     FastqOutputFormat, FastqRecordWriter, QseqOutputFormat, QseqRecordWriter, convert)
+from .summarize import (  # noqa: F401
+    SummarizeOutputFormat, SummarizeReducer, SummaryGroup, getSummaryName, summarize, summary_sort)
 from .vcf_text import (  # noqa: F401
     KeyIgnoringVCFOutputFormat, KeyIgnoringVCFRecordWriter, VCFHeader, VCFOutputFormat, VCFRecordWriter,
     VCFUnsupportedException, read_vcf_header_from)

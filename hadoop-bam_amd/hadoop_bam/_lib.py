@@ -73,6 +73,7 @@ EXPORTS = [
     "hbam_bcf_header_text", "hbam_vcf_render",
     "hbam_fasta_sections", "hbam_fasta_decode_split", "hbam_fasta_columns_to_host", "hbam_fasta_release",
     "hbam_chain_table",
+    "hbam_summarize_reduce", "hbam_summary_keys", "hbam_summary_gather_lines", "hbam_device_copy",
 ]
 
 # hbam_read_fn: int64_t read(void* user, uint64_t offset, uint64_t len, uint8_t* dst)
@@ -127,6 +128,17 @@ class FixmateRunC(C.Structure):
     _fields_ = [("n", C.c_uint64), ("payload_bytes", C.c_uint64), ("n_groups", C.c_uint64),
                 ("status", C.c_int32), ("pad", C.c_int32), ("src", C.c_void_p), ("mate", C.c_void_p),
                 ("offsets", C.c_void_p), ("payload", C.c_void_p)]
+
+
+class SummaryC(C.Structure):
+    _fields_ = [("n_streams", C.c_uint64), ("n_lines", C.c_uint64), ("text_len", C.c_uint64),
+                ("n_segments", C.c_uint64), ("first", C.c_void_p), ("rid", C.c_void_p), ("beg", C.c_void_p),
+                ("end", C.c_void_p), ("count", C.c_void_p), ("text", C.c_void_p), ("text_off", C.c_void_p)]
+
+
+class SummaryLinesC(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("status", C.c_int32), ("pad", C.c_int32), ("text", C.c_void_p),
+                ("start", C.c_void_p), ("len", C.c_void_p), ("key", C.c_void_p)]
 
 
 class BcfHeaderC(C.Structure):
@@ -342,6 +354,12 @@ def load(path=None):
                                             C.POINTER(BcfHeaderC), C.c_uint64, C.c_uint64,
                                             C.POINTER(BcfColumnsC)]),
         "hbam_summarize_ranges": (C.c_int, [vp, C.POINTER(Columns), C.POINTER(RangesC)]),
+        "hbam_summarize_reduce": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int,
+                                            C.POINTER(SummaryC)]),
+        "hbam_device_copy": (C.c_int, [vp, vp, vp, C.c_uint64]),
+        "hbam_summary_keys": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.POINTER(SummaryLinesC)]),
+        "hbam_summary_gather_lines": (C.c_int, [vp, C.POINTER(SummaryLinesC), vp, C.c_uint64, vp, C.c_uint64, vp,
+                                                C.POINTER(C.c_uint64)]),
         "hbam_name_order": (C.c_int, [vp, vp, vp, C.c_uint64, vp]),
         "hbam_fixmate": (C.c_int, [vp, vp, vp, C.c_uint64, C.POINTER(FixmateRunC)]),
         "hbam_bgzf_compress": (C.c_int64, [vp, vp, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int,
@@ -1039,6 +1057,119 @@ class Context:
                     offsets=self._d2h(r.offsets, k + 1, np.uint64) if k else np.zeros(1, np.uint64),
                     src=self._d2h(r.src, k, np.uint32), mate=self._d2h(r.mate, k, np.uint32),
                     n_groups=int(r.n_groups), status=int(r.status))
+
+    # ---- the summarize plugin's reduce side and SummarySort ------------------------------------
+    def device_alloc(self, nbytes):
+        """hbam_device_alloc -> DeviceBuffer (freed by free())."""
+        b = C.c_void_p()
+        rc = self.L.hbam_device_alloc(self.h, int(nbytes), C.byref(b))
+        if rc:
+            raise RuntimeError("hbam_device_alloc failed (%d): %s" % (rc, self.last_error()))
+        return DeviceBuffer(self, b.value, nbytes, True)
+
+    def device_copy(self, dst_ptr, src_ptr, nbytes):
+        rc = self.L.hbam_device_copy(self.h, C.c_void_p(dst_ptr), C.c_void_p(src_ptr), int(nbytes))
+        if rc:
+            raise RuntimeError("hbam_device_copy failed (%d): %s" % (rc, self.last_error()))
+
+    def summarize_reduce_device(self, key_ptr, beg_ptr, end_ptr, rev_ptr, n, levels, sort_output=False):
+        """hbam_summarize_reduce over n device-resident ranges -> SummaryC (device memory owned by
+        the context until the next call)."""
+        lv = np.ascontiguousarray(levels, np.int32)
+        s = SummaryC()
+        rc = self.L.hbam_summarize_reduce(self.h, C.c_void_p(key_ptr), C.c_void_p(beg_ptr), C.c_void_p(end_ptr),
+                                          C.c_void_p(rev_ptr), int(n), C.c_void_p(lv.ctypes.data), len(lv),
+                                          int(bool(sort_output)), C.byref(s))
+        if rc:
+            raise RuntimeError("hbam_summarize_reduce failed (%d): %s" % (rc, self.last_error()))
+        return s
+
+    def summary_to_host(self, s):
+        k, m = int(s.n_streams), int(s.n_lines)
+        return dict(first=self._d2h(s.first, k + 1, np.uint64), rid=self._d2h(s.rid, m, np.int32),
+                    beg=self._d2h(s.beg, m, np.int32), end=self._d2h(s.end, m, np.int32),
+                    count=self._d2h(s.count, m, np.int32),
+                    text=self._d2h(s.text, int(s.text_len), np.uint8).tobytes(),
+                    text_off=self._d2h(s.text_off, k + 1, np.uint64), n_segments=int(s.n_segments))
+
+    def summarize_reduce(self, key, beg, end, rev, levels, sort_output=False):
+        """hbam_summarize_reduce over host arrays (uploaded) -> host dict(first, rid, beg, end,
+        count, text, text_off, n_segments, timing)."""
+        arrs = [np.ascontiguousarray(key, np.int64), np.ascontiguousarray(beg, np.int32),
+                np.ascontiguousarray(end, np.int32), np.ascontiguousarray(rev, np.uint8)]
+        n = len(arrs[0])
+        bufs = [self.upload(a.view(np.uint8)) for a in arrs]
+        try:
+            s = self.summarize_reduce_device(bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, n, levels,
+                                             sort_output)
+            t = self.timing()
+            out = self.summary_to_host(s)
+            out["timing"] = t
+            return out
+        finally:
+            for b in bufs:
+                b.free()
+
+    def summary_keys_device(self, text):
+        """hbam_summary_keys -> SummaryLinesC (device memory owned by the context); `text` must stay
+        alive while the result is used when it is device-resident."""
+        p, n, dev, keep = self._ptr(text)
+        s = SummaryLinesC()
+        rc = self.L.hbam_summary_keys(self.h, p, dev, n, C.byref(s))
+        if rc:
+            raise RuntimeError("hbam_summary_keys failed (%d): %s" % (rc, self.last_error()))
+        return s
+
+    def summary_gather_lines(self, lines, perm=None, n=None):
+        """hbam_summary_gather_lines: lines perm[0..n) (a device pointer, or None for the identity),
+        each followed by a newline -> a DeviceBuffer of the text (free() it)."""
+        n = int(lines.n) if n is None else int(n)
+        off = self.device_alloc(8 * (n + 1))
+        try:
+            tot = C.c_uint64(0)
+            rc = self.L.hbam_summary_gather_lines(self.h, C.byref(lines), perm, n, None, 0, C.c_void_p(off.ptr),
+                                                  C.byref(tot))
+            if rc:
+                raise RuntimeError("hbam_summary_gather_lines failed (%d): %s" % (rc, self.last_error()))
+            out = self.device_alloc(max(int(tot.value), 1))
+            out.nbytes = int(tot.value)
+            rc = self.L.hbam_summary_gather_lines(self.h, C.byref(lines), perm, n, C.c_void_p(out.ptr), tot.value,
+                                                  C.c_void_p(off.ptr), C.byref(tot))
+            if rc:
+                out.free()
+                raise RuntimeError("hbam_summary_gather_lines failed (%d): %s" % (rc, self.last_error()))
+            return out
+        finally:
+            off.free()
+
+    def summary_keys(self, text, sort=False):
+        """hbam_summary_keys over `text` -> host dict(n, status, start, len, key, lines): `lines`
+        = the n lines gathered in file order, or (sort) in the stable order of their keys."""
+        dtext = self.upload(text) if not isinstance(text, DeviceBuffer) else text
+        try:
+            s = self.summary_keys_device(dtext)
+            n = int(s.n)
+            out = dict(n=n, status=int(s.status), start=self._d2h(s.start, n, np.uint32),
+                       len=self._d2h(s.len, n, np.uint32), key=self._d2h(s.key, n, np.int64))
+            perm = None
+            pbuf = None
+            if sort and n:
+                pbuf = self.device_alloc(4 * n)
+                rc = self.L.hbam_sort_keys(self.h, C.c_void_p(s.key), n, None, C.c_void_p(pbuf.ptr))
+                if rc:
+                    raise RuntimeError("hbam_sort_keys failed (%d): %s" % (rc, self.last_error()))
+                perm = C.c_void_p(pbuf.ptr)
+            try:
+                g = self.summary_gather_lines(s, perm, n)
+                out["lines"] = self._d2h(g.ptr, g.nbytes, np.uint8).tobytes()
+                g.free()
+            finally:
+                if pbuf is not None:
+                    pbuf.free()
+            return out
+        finally:
+            if dtext is not text:
+                dtext.free()
 
     # ---- BCF over BGZF (SURVEY.md §8 f-3) --------------------------------------------------------
     def bcf_parse_header(self, file_prefix):

@@ -527,6 +527,78 @@ typedef struct hbam_fixmate_run {
 int hbam_fixmate(hbam_ctx* ctx, const uint8_t* ubuf, const uint64_t* rec_off, uint64_t n,
                  hbam_fixmate_run* out);
 
+/* copy `bytes` between two device ranges (library-owned or caller-owned), ordered after the
+ * context's work: how a caller keeps a call's context-owned output across the next call */
+int hbam_device_copy(hbam_ctx* ctx, void* dst, const void* src, uint64_t bytes);
+
+/* ---- the summarize plugin's reduce side and SummarySort (cli/plugins/chipster) -----------------
+ * SummarizeReducer (Summarize.java:466-561) as ONE reducer over the whole job.  key / beg / end / rev
+ * (device, n < 2^32 entries) are the ranges of every hbam_summarize_ranges call of the job, in
+ * input order (split order, record order, range order): the caller copies them out of the
+ * context-owned buffers between windows.  The call orders them by key with hbam_sort_keys (equal
+ * keys keep input order: the documented tie-break, the reference leaves it unspecified), cuts the
+ * stream into segments where (int)(key >>> 32) changes, and for every level L (levels: host,
+ * n_levels positive int32) and strand cuts the strand's ranges of a segment into consecutive
+ * groups of L.  A group is one RangeCount: beg = (int)(sumBeg / count), end = (int)(sumEnd / count)
+ * with Java long sums and truncating division, count = the group's size, rid = the segment's
+ * referenceID -- except that a trailing partial group flushed at a segment change carries the
+ * referenceID of the NEXT segment (reduce() updates currentReferenceID before doAllSummaries(),
+ * :508-511); the last segment's partial groups, flushed by cleanup(), carry their own.
+ * The 2 * n_levels output streams are ordered level-major, forward strand ('f') then reverse
+ * ('r'); stream k holds lines [first[k], first[k + 1]) in segment order, then group order, and its
+ * text (RangeCount.toString + '\n' per line) is text[text_off[k], text_off[k + 1]).
+ * sort_output != 0: each stream's lines are put in SummarySort's order first, a stable sort by
+ * getKey0(rid, beg) (its sign extension kept: a negative beg makes the key's high word -1).
+ * out is device memory owned by the context until the next call.  n == 0 is valid: empty streams.
+ * Timing: total_ms, scan_ms = the shuffle's radix sort, walk_ms = sort_output's sorts, n_records = n,
+ * n_blocks = the lines, pool_bytes = the text's bytes. */
+typedef struct hbam_summary {
+  uint64_t n_streams;  /* 2 * n_levels */
+  uint64_t n_lines;
+  uint64_t text_len;
+  uint64_t n_segments;
+  uint64_t* first;     /* n_streams + 1 */
+  int32_t* rid;        /* n_lines each */
+  int32_t* beg;
+  int32_t* end;
+  int32_t* count;
+  uint8_t* text;
+  uint64_t* text_off;  /* n_streams + 1 */
+} hbam_summary;
+int hbam_summarize_reduce(hbam_ctx* ctx, const int64_t* key, const int32_t* beg, const int32_t* end,
+                          const uint8_t* rev, uint64_t n, const int32_t* levels, uint32_t n_levels,
+                          int sort_output, hbam_summary* out);
+/* SortRecordReader.nextKeyValue (chipster/SummarySort.java:240-260) over an inflated summary file
+ * read as one split: text (host or device per on_device, at most 2^31 bytes, the 64-byte rule).
+ * Lines are Hadoop LineReader lines: LF, a lone CR and CRLF end a line, a last line without a
+ * terminator is a line, an empty line is a line.  Per line tabOne / tabTwo are its first two tabs,
+ * rid = parseInt(line[0, tabOne)), pos = parseInt(line(tabOne, tabTwo)), key = getKey0(rid, pos).
+ * status = the exception nextKeyValue raises after the first n lines, in file order, checked in
+ * the Java's order: no tab HBAM_EINDEX (Text.decode with a negative length), rid not an int
+ * HBAM_ENUMBER, no second tab HBAM_EINDEX, pos not an int HBAM_ENUMBER (a byte >= 0x80 inside a
+ * field too; both choices unpinned).  start / len (without the terminator) / key cover
+ * the n lines; text is the window on the device.  All owned by the context until the next call
+ * that reads text.  Timing: scan_ms = structural pass, total_ms, ubuf_bytes, n_records. */
+typedef struct hbam_summary_lines {
+  uint64_t n;
+  int32_t status;
+  int32_t pad;
+  const uint8_t* text;
+  uint32_t* start;
+  uint32_t* len;
+  int64_t* key;
+} hbam_summary_lines;
+int hbam_summary_keys(hbam_ctx* ctx, const uint8_t* text, int on_device, uint64_t len,
+                      hbam_summary_lines* out);
+/* SortOutputFormat's text: lines perm[0..n) of a hbam_summary_keys result (perm: device u32 indices
+ * below lines->n, NULL = identity), each followed by '\n' (CRLF input comes out LF, as
+ * TextOutputFormat writes it), packed into out (device); out_off (device, u64[n+1]) gets the
+ * exclusive scan of the lengths + 1.  out == NULL: size query (total_bytes only), as
+ * hbam_gather_records.  Timing: pools_ms, pool_bytes. */
+int hbam_summary_gather_lines(hbam_ctx* ctx, const hbam_summary_lines* lines, const uint32_t* perm,
+                              uint64_t n, uint8_t* out, uint64_t out_cap, uint64_t* out_off,
+                              uint64_t* total_bytes);
+
 /* ---- diagnostics (no reference counterpart) -----------------------------------------------
  * hbam_resolve_tokens: the LZ77 pass of the batched inflate (k_resolve) over ONE caller-built
  * token block: `io` (host, isize <= 65536 bytes) holds literal bytes with a 3-byte descriptor
