@@ -321,43 +321,23 @@ extern "C" int hbam_bcf_decode_split(hbam_ctx* c, const uint8_t* comp, int on_de
     if ((rc = build_chain(c, d, comp_len, coff_s - comp_base, window_is_file_end, &ch))) return rc;
     const uint64_t nb = ch.nb;
     if (nb == 0) {  // initialize(): bci.seek(virtualStart) fails, or an empty stream
-      if (ch.end_code == HBAM_EMORE) {
-        out->status = HBAM_EMORE;
-        return HBAM_OK;
-      }
-      if (ch.end_code == HBAM_EEOF) {
-        out->status = uoff_s != 0 ? HBAM_EIO : HBAM_OK;
-        return HBAM_OK;
-      }
-      out->status = ch.end_code == HBAM_ERUNTIMEIO ? HBAM_EIO : ch.end_code;
+      out->status = bgzf_seek(0, ch.end_code, NO_BLOCK, HBAM_EEOF, nullptr, uoff_s, comp_base, file_len).status;
       return HBAM_OK;
     }
-    BlockRec* blk = (BlockRec*)c->bufs[B_BLK].p;
-    uint32_t* isz;
-    uint64_t* uoff;
-    uint64_t* small;
-    if ((rc = ensure(c, B_ISZ32, nb + 1, &isz)) || (rc = ensure(c, B_UOFF, nb + 1, &uoff)) ||
-        (rc = ensure(c, B_SMALL, 16, &small)))
-      return rc;
-    HIPCHK(c, hipMemsetAsync(small, 0xff, 8 * 8, c->stream));
-    k_isize32<<<grid_for(nb, 256), 256, 0, c->stream>>>(blk, nb, isz, (uint32_t*)small);
-    uint64_t utotal = 0;
-    if ((rc = scan_exclusive<uint32_t>(c, isz, nb, uoff, &utotal))) return rc;
-    std::vector<BlockRec> hb(nb);
+    // ---- blocks: sizes, and the whole table on the host (the replays below walk it)
+    BgzfSplit bs;
+    if ((rc = bgzf_sizes(c, nb, nb, &bs))) return rc;
+    const std::vector<BlockRec>& hb = bs.hb;
     std::vector<uint64_t> hu(nb + 1);
-    HIPCHK(c, hipMemcpyAsync(hb.data(), blk, nb * sizeof(BlockRec), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(hu.data(), uoff, (nb + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->pinned_small, small, 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const uint32_t bigi = (uint32_t)(c->pinned_small[0] & 0xffffffffu);
-    // bci.seek(virtualStart): the block at coff_s, or the next one when it is empty
-    const uint64_t sblk = hb[0].isize == 0 ? 1 : 0;
+    HIPCHK(c, copy_sync(c, hu.data(), bs.uoff, (nb + 1) * 8, hipMemcpyDeviceToHost));
+    const uint64_t sblk = bgzf_seek_block(hb[0]);
     // Where BGZFLimitingStream stops (the replay needs block sizes only): with every block assumed
     // to inflate, the stream ends at z0; only the blocks up to z0's (and one more) are inflated, so
     // a split costs its own blocks, not the rest of the file.  A block failing before
     // that point ends the stream earlier: the replay runs again with it (z only moves back).
     uint64_t z0 = 0;
     int32_t zc0 = HBAM_OK;
+    uint64_t nbi = std::min<uint64_t>(nb, 2);  // blocks inflated
     if (sblk < nb) {
       r0 = hu[sblk] + uoff_s;
       const BcfBlocks B0{&hb, comp_base, nb, nb, HBAM_OK, ch.end_code};
@@ -367,53 +347,19 @@ extern "C" int hbam_bcf_decode_split(hbam_ctx* c, const uint8_t* comp, int on_de
         out->status = HBAM_EMORE;
         return HBAM_OK;
       }
-    }
-    uint64_t nbi = nb;  // blocks inflated
-    if (sblk < nb) {
       uint64_t zb = sblk;
       while (zb + 1 < nb && hu[zb + 1] <= z0) ++zb;
       nbi = std::min<uint64_t>(nb, zb + 2);
-    } else {
-      nbi = std::min<uint64_t>(nb, 2);
     }
-    const uint64_t ui = hu[nbi];
-    uint8_t* ubw;
-    int32_t* st;
-    uint32_t* crc;
-    if ((rc = ensure(c, B_UBUF, ui + UBUF_SLACK, &ubw)) || (rc = ensure(c, B_INFST, nbi + 1, &st)) ||
-        (rc = ensure(c, B_CRC, nbi + 1, &crc)))
-      return rc;
-    if ((rc = inflate_blocks(c, d, blk, nbi, uoff, ubw, st, false, crc))) return rc;
-    unsigned long long* first_bad = (unsigned long long*)small + 1;
-    k_first_bad_block<<<grid_for(nbi, 256), 256, 0, c->stream>>>(st, crc, blk, nbi, 0, first_bad);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->pinned_small, small, 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    uint64_t fb = c->pinned_small[1];
-    int32_t fb_code = HBAM_EEOF;
-    if (fb != ~0ULL) {
-      int32_t s;
-      HIPCHK(c, copy_sync(c, &s, st + fb, 4, hipMemcpyDeviceToHost));
-      fb_code = (s == INF_DATA) ? HBAM_EDATA : HBAM_EFORMAT;
-    }
-    if (bigi != 0xffffffffu && bigi < nbi && (fb == ~0ULL || bigi < fb)) {
-      fb = bigi;
-      fb_code = HBAM_EUNSUPPORTED;
-    }
-    if (fb == ~0ULL) fb = nb;
-    if (fb == 0) { out->status = fb_code; return HBAM_OK; }
-    if (sblk >= nb) {
-      if (ch.end_code != HBAM_EEOF) { out->status = ch.end_code == HBAM_ERUNTIMEIO ? HBAM_EIO : ch.end_code; return HBAM_OK; }
-      out->status = uoff_s != 0 ? HBAM_EIO : HBAM_OK;
+    // ---- inflate those (no CRC check), the first that fails, bci.seek(virtualStart)
+    if ((rc = bgzf_inflate(c, d, nbi, hu[nbi], false, &bs))) return rc;
+    const SeekOutcome sk = bgzf_seek(nb, ch.end_code, bs.fb, bs.fb_code, hb.data(), uoff_s, comp_base, file_len);
+    if (sk.ends) {
+      out->status = sk.status;
       return HBAM_OK;
     }
-    if (fb == sblk) { out->status = fb_code; return HBAM_OK; }
-    {
-      const BlockRec& bs = hb[sblk];
-      const uint64_t after = comp_base + bs.coff + bs.clen;
-      const bool eof = (after == file_len) || (file_len - after == 28);
-      if (uoff_s > bs.isize || (uoff_s == bs.isize && !eof)) { out->status = HBAM_EIO; return HBAM_OK; }
-    }
+    const uint64_t fb = bs.fb == NO_BLOCK ? nb : bs.fb;
+    const int32_t fb_code = bs.fb_code;
     z = z0;
     z_code = zc0;
     if (fb < nb) {
@@ -421,9 +367,9 @@ extern "C" int hbam_bcf_decode_split(hbam_ctx* c, const uint8_t* comp, int on_de
       if ((rc = bcf_stream_end(B, sblk, uoff_s, r0, v_end, &z, &z_code)))
         return set_err(c, rc, "BGZFLimitingStream with vEnd & 0xffff == 0 never returns");
     }
-    ub = ubw;
-    ulen = ui;
-    uo = uoff + sblk;
+    ub = bs.ub;
+    ulen = hu[nbi];
+    uo = bs.uoff + sblk;
     wb = nbi - sblk;
     rel_base = r0;
   } else {
@@ -451,52 +397,11 @@ extern "C" int hbam_bcf_decode_split(hbam_ctx* c, const uint8_t* comp, int on_de
   uint64_t nrec = 0, exit_last = r0;
   uint64_t* rec_off = nullptr;
   if (wb && r0 < ulen) {
-    uint64_t *entry, *exitp, *rbase;
-    uint16_t* rel;
-    uint32_t *count, *badlist, *nbad_d;
-    uint8_t* mark;
-    uint64_t* small;
-    if ((rc = ensure(c, B_ENTRY, wb + 1, &entry)) || (rc = ensure(c, B_EXIT, wb + 1, &exitp)) ||
-        (rc = ensure(c, B_REL, wb * WALK_CAP, &rel)) || (rc = ensure(c, B_COUNT, wb + 1, &count)) ||
-        (rc = ensure(c, B_RECBASE, wb + 1, &rbase)) || (rc = ensure(c, B_BADLIST, wb + 1, &badlist)) ||
-        (rc = ensure(c, B_MARK, wb + 1, &mark)) || (rc = ensure(c, B_SMALL, 16, &small)))
-      return rc;
-    const BcfFmt fmt{bh};
-    const uint64_t hard_end = z;
-    if (wb > 1) k_block_entry<<<(uint32_t)(wb - 1), 64, 0, c->stream>>>(ub, uo, (uint32_t)wb, hard_end, fmt, entry);
-    k_block_walk<<<grid_for(wb, 64), 64, 0, c->stream>>>(ub, uo, (uint32_t)wb, r0, hard_end, fmt, entry, rel, count,
-                                                         exitp);
-    nbad_d = (uint32_t*)(small + 5);
-    HIPCHK(c, hipMemsetAsync(nbad_d, 0, 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(mark, 0, 1, c->stream));
-    if (wb > 1)
-      k_stitch_check<<<grid_for(wb - 1, 256), 256, 0, c->stream>>>(entry, exitp, (uint32_t)wb, nbad_d, badlist,
-                                                                   (uint32_t)wb, mark);
-    uint32_t nbad = 0;
-    HIPCHK(c, hipMemcpyAsync(&nbad, nbad_d, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (nbad) {
-      k_chain_fix_par<<<grid_for(nbad, 64), 64, 0, c->stream>>>(ub, uo, (uint32_t)wb, hard_end, fmt, entry, rel,
-                                                                 count, exitp, badlist, nbad, mark);
-      HIPCHK(c, hipMemsetAsync(nbad_d, 0, 4, c->stream));
-      k_stitch_check<<<grid_for(wb - 1, 256), 256, 0, c->stream>>>(entry, exitp, (uint32_t)wb, nbad_d, badlist,
-                                                                   (uint32_t)wb, nullptr);
-      HIPCHK(c, hipMemcpyAsync(&nbad, nbad_d, 4, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    if (nbad) {
-      std::vector<uint32_t> bl(nbad);
-      HIPCHK(c, copy_sync(c, bl.data(), badlist, nbad * 4, hipMemcpyDeviceToHost));
-      std::sort(bl.begin(), bl.end());
-      HIPCHK(c, copy_sync(c, badlist, bl.data(), nbad * 4, hipMemcpyHostToDevice));
-      k_chain_fix<<<1, 64, 0, c->stream>>>(ub, uo, (uint32_t)wb, hard_end, fmt, entry, rel, count, exitp, badlist,
-                                           nbad);
-      HIPCHK(c, hipGetLastError());
-    }
-    if ((rc = scan_exclusive<uint32_t>(c, count, wb, rbase, &nrec))) return rc;
-    HIPCHK(c, copy_sync(c, &exit_last, exitp + (wb - 1), 8, hipMemcpyDeviceToHost));
+    ChainWalk w;
+    if ((rc = walk_chain(c, ub, uo, wb, r0, z, BcfFmt{bh}, &w, nullptr, &exit_last))) return rc;
+    nrec = w.nrec;
     if ((rc = ensure(c, B_RECOFF, nrec + 1, &rec_off))) return rc;
-    k_emit_rec_off<<<(uint32_t)wb, 256, 0, c->stream>>>(uo, (uint32_t)wb, rel, count, rbase, rec_off);
+    k_emit_rec_off<<<(uint32_t)wb, 256, 0, c->stream>>>(uo, (uint32_t)wb, w.rel, w.count, w.rbase, rec_off);
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
@@ -505,7 +410,7 @@ extern "C" int hbam_bcf_decode_split(hbam_ctx* c, const uint8_t* comp, int on_de
   if ((rc = bcf_cols(c, nrec, &bc))) return rc;
   uint64_t* small;
   if ((rc = ensure(c, B_SMALL, 16, &small))) return rc;
-  unsigned long long* first_stop = (unsigned long long*)small + 6;
+  unsigned long long* first_stop = (unsigned long long*)small + SM_FIRST_STOP;
   HIPCHK(c, hipMemsetAsync(first_stop, 0xff, 8, c->stream));
   if (nrec)
     k_bcf_decode<<<grid_for(nrec, 256), 256, 0, c->stream>>>(ub, nrec, rec_off, z, z_code, limit, rel_base,

@@ -1281,6 +1281,11 @@ float ev_ms(hbam_ctx* c, int a, int b) {
 // that round trip (into pinned_small[PS_ALSO_READ]): k_decode_fixed's first stop where the caller
 // has not read it yet (SAM text), and a stop below n there ends the call before the pools.
 constexpr int PS_POOL_TOTALS = 96, PS_ALSO_READ = 100;
+// The other fixed slots of pinned_small, and the words of B_SMALL, that the split decoders and
+// their shared pieces (bgzf_sizes, bgzf_inflate, walk_chain) use: disjoint, so that a helper's
+// readback never lands on a value its caller still holds.
+constexpr int PS_FIRST_BAD = 0, PS_UTOTAL = 64, PS_BLOCKS = 66, PS_NBAD = 80, PS_WALK_ALSO = 81;
+constexpr int SM_BIG_ISIZE = 0, SM_FIRST_BAD = 1, SM_NBAD = 5, SM_FIRST_STOP = 6;
 int finish_pools(hbam_ctx* c, const uint8_t* ub, uint64_t n, const uint64_t* rec_off, DevColumns& dc,
                  const uint64_t* also_read = nullptr) {
   int rc;
@@ -1358,6 +1363,180 @@ void columns_out(hbam_columns* out, const DevColumns& dc, uint64_t* voff, uint64
   out->aux = dc.aux;
 }
 
+// ---- the BGZF split front end and the record-chain walk (BAM and BCF splits) ----------------
+constexpr uint64_t NO_BLOCK = ~0ULL;
+
+struct BgzfSplit {
+  uint64_t nb = 0;            // blocks of the chain (B_BLK)
+  BlockRec* blk = nullptr;
+  uint64_t* uoff = nullptr;   // [nb + 1]: where each block's bytes start in ubuf (ISIZE > 64 KiB: none)
+  uint64_t* small = nullptr;
+  uint64_t utotal = 0;        // uoff[nb]
+  std::vector<BlockRec> hb;   // the first blocks, host view
+  uint8_t* ub = nullptr;      // after bgzf_inflate: the inflated bytes, per-block status and CRC,
+  int32_t* st = nullptr;
+  uint32_t* crc = nullptr;
+  uint64_t fb = NO_BLOCK;     // the first block whose read throws, and what it throws
+  int32_t fb_code = HBAM_EEOF;
+};
+
+// From build_chain's block table (nb >= 1) to the sizes: ISIZE clamp, ubuf offsets, and in one round
+// trip the inflated total and the first n_host block records.
+int bgzf_sizes(hbam_ctx* c, uint64_t nb, uint64_t n_host, BgzfSplit* s) {
+  int rc;
+  uint32_t* isz;
+  s->nb = nb;
+  s->blk = (BlockRec*)c->bufs[B_BLK].p;
+  if ((rc = ensure(c, B_ISZ32, nb + 1, &isz))) return rc;
+  if ((rc = ensure(c, B_UOFF, nb + 1, &s->uoff))) return rc;
+  if ((rc = ensure(c, B_SMALL, 16, &s->small))) return rc;
+  HIPCHK(c, hipMemsetAsync(s->small, 0xff, 8 * 8, c->stream));
+  HIPCHK(c, hipMemsetAsync(s->small + 8, 0, 8 * 8, c->stream));
+  k_isize32<<<grid_for(nb, 256), 256, 0, c->stream>>>(s->blk, nb, isz, (uint32_t*)(s->small + SM_BIG_ISIZE));
+  if ((rc = scan_exclusive<uint32_t>(c, isz, nb, s->uoff, nullptr))) return rc;
+  n_host = std::min(n_host, nb);
+  s->hb.resize(n_host);
+  // two records fit the pinned slots; a whole table goes straight to the vector
+  void* hdst = n_host <= 2 ? (void*)(c->pinned_small + PS_BLOCKS) : (void*)s->hb.data();
+  HIPCHK(c, hipMemcpyAsync(c->pinned_small + PS_UTOTAL, s->uoff + nb, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(hdst, s->blk, n_host * sizeof(BlockRec), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  s->utotal = c->pinned_small[PS_UTOTAL];
+  if (n_host <= 2) memcpy(s->hb.data(), hdst, n_host * sizeof(BlockRec));
+  return HBAM_OK;
+}
+
+// Inflate blocks [0, nbi) into ubuf (ubytes = uoff[nbi]) between events 2 and 3, then the first block
+// among them whose read throws: a failed inflate or CRC, or an ISIZE above 64 KiB (EUNSUPPORTED)
+// where that block comes first.  An oversized block at or past nbi was not read: it does not count.
+int bgzf_inflate(hbam_ctx* c, const uint8_t* d, uint64_t nbi, uint64_t ubytes, bool check_crc, BgzfSplit* s) {
+  int rc;
+  if ((rc = ensure(c, B_UBUF, ubytes + UBUF_SLACK, &s->ub))) return rc;
+  if ((rc = ensure(c, B_INFST, nbi + 1, &s->st))) return rc;
+  if ((rc = ensure(c, B_CRC, nbi + 1, &s->crc))) return rc;
+  HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
+  if ((rc = inflate_blocks(c, d, s->blk, nbi, s->uoff, s->ub, s->st, check_crc, s->crc))) return rc;
+  HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+  k_first_bad_block<<<grid_for(nbi, 256), 256, 0, c->stream>>>(s->st, s->crc, s->blk, nbi, check_crc ? 1 : 0,
+                                                              (unsigned long long*)s->small + SM_FIRST_BAD);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(c->pinned_small + PS_FIRST_BAD, s->small, 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint32_t bigi = (uint32_t)(c->pinned_small[PS_FIRST_BAD + SM_BIG_ISIZE] & 0xffffffffu);
+  s->fb = c->pinned_small[PS_FIRST_BAD + SM_FIRST_BAD];
+  s->fb_code = HBAM_EEOF;
+  if (s->fb != NO_BLOCK) {
+    int32_t st;
+    HIPCHK(c, copy_sync(c, &st, s->st + s->fb, 4, hipMemcpyDeviceToHost));
+    s->fb_code = (st == INF_DATA) ? HBAM_EDATA : HBAM_EFORMAT;
+  }
+  if (bigi != 0xffffffffu && bigi < nbi && (s->fb == NO_BLOCK || bigi < s->fb)) {
+    s->fb = bigi;
+    s->fb_code = HBAM_EUNSUPPORTED;
+  }
+  return HBAM_OK;
+}
+
+// BlockCompressedInputStream.seek(vStart) over the block table: no device work.  Either the call
+// ends with `status`, or reading starts in block sblk at ubuf offset r0.
+//   nb, end_code   the chain: its blocks and what reading past the last one raises
+//   fb, fb_code    the first block whose read throws (NO_BLOCK: none)
+//   b0             the first min(nb, 2) block records
+//   uoff_s         vStart & 0xffff
+inline uint64_t bgzf_seek_block(const BlockRec& b0) { return b0.isize == 0 ? 1 : 0; }  // empty: the next
+struct SeekOutcome {
+  bool ends;
+  int32_t status;
+  uint64_t sblk, r0;
+};
+SeekOutcome bgzf_seek(uint64_t nb, int32_t end_code, uint64_t fb, int32_t fb_code, const BlockRec* b0,
+                      uint32_t uoff_s, uint64_t comp_base, uint64_t file_len) {
+  const auto ends = [](int32_t status) { return SeekOutcome{true, status, 0, 0}; };
+  // readBlock where the chain has ended (at vStart's block, or in available() after an empty last
+  // block): its exception, or count == 0, an empty current block, where only offset 0 is valid
+  const auto past_chain = [&] {
+    if (end_code != HBAM_EEOF) return ends(end_code == HBAM_ERUNTIMEIO ? HBAM_EIO : end_code);
+    return ends(uoff_s != 0 ? HBAM_EIO : HBAM_OK);
+  };
+  if (nb == 0) return past_chain();
+  const uint64_t sblk = bgzf_seek_block(b0[0]);
+  if (fb == 0 || fb == sblk) return ends(fb_code);
+  if (sblk >= nb) return past_chain();
+  const BlockRec& bs = b0[sblk];
+  const uint64_t after = comp_base + bs.coff + bs.clen;  // file position after the block
+  const bool eof = (after == file_len) || (file_len - after == 28);
+  if (uoff_s > bs.isize || (uoff_s == bs.isize && !eof)) return ends(HBAM_EIO);
+  // uoff[sblk] is 0: sblk is 1 only when block 0 is empty (uoff[1] = ISIZE 0)
+  return SeekOutcome{false, HBAM_OK, sblk, uoff_s};
+}
+
+// The record chain over walk segments uo[0..wb] of ub (wb >= 1), from r0 up to hard_end, in the
+// framing fmt (BamFmt, BcfFmt): every segment walked from a guessed entry, the stitches checked,
+// mismatched runs repaired in parallel and what is left in order, then the counts scanned.  The
+// caller's emit kernel turns (rel, count, rbase) into record offsets.  also_read: a device word of
+// the caller's read back with the stitch count (into w->also); last_exit: exitp[wb - 1] at the end.
+struct ChainWalk {
+  uint64_t *entry, *exitp, *rbase;
+  uint16_t* rel;
+  uint32_t* count;
+  uint64_t nrec, also;
+};
+template <typename Fmt>
+int walk_chain(hbam_ctx* c, const uint8_t* ub, const uint64_t* uo, uint64_t wb, uint64_t r0, uint64_t hard_end,
+               Fmt fmt, ChainWalk* w, const uint64_t* also_read = nullptr, uint64_t* last_exit = nullptr) {
+  int rc;
+  uint32_t* badlist;
+  uint8_t* mark;
+  uint64_t* small;
+  if ((rc = ensure(c, B_ENTRY, wb + 1, &w->entry))) return rc;
+  if ((rc = ensure(c, B_EXIT, wb + 1, &w->exitp))) return rc;
+  if ((rc = ensure(c, B_REL, wb * WALK_CAP, &w->rel))) return rc;
+  if ((rc = ensure(c, B_COUNT, wb + 1, &w->count))) return rc;
+  if ((rc = ensure(c, B_RECBASE, wb + 1, &w->rbase))) return rc;
+  if ((rc = ensure(c, B_BADLIST, wb + 1, &badlist))) return rc;
+  if ((rc = ensure(c, B_MARK, wb + 1, &mark))) return rc;
+  if ((rc = ensure(c, B_SMALL, 16, &small))) return rc;
+  uint32_t* nbad_d = (uint32_t*)(small + SM_NBAD);
+  if (wb > 1)
+    k_block_entry<<<(uint32_t)(wb - 1), 64, 0, c->stream>>>(ub, uo, (uint32_t)wb, hard_end, fmt, w->entry);
+  k_block_walk<<<grid_for(wb, 64), 64, 0, c->stream>>>(ub, uo, (uint32_t)wb, r0, hard_end, fmt, w->entry, w->rel,
+                                                       w->count, w->exitp);
+  HIPCHK(c, hipMemsetAsync(nbad_d, 0, 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(mark, 0, 1, c->stream));  // block 0 (the split start) is never listed
+  if (wb > 1)
+    k_stitch_check<<<grid_for(wb - 1, 256), 256, 0, c->stream>>>(w->entry, w->exitp, (uint32_t)wb, nbad_d, badlist,
+                                                                 (uint32_t)wb, mark);
+  HIPCHK(c, hipMemcpyAsync(c->pinned_small + PS_NBAD, nbad_d, 4, hipMemcpyDeviceToHost, c->stream));
+  if (also_read)
+    HIPCHK(c, hipMemcpyAsync(c->pinned_small + PS_WALK_ALSO, also_read, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  uint32_t nbad = (uint32_t)c->pinned_small[PS_NBAD];
+  if (also_read) w->also = c->pinned_small[PS_WALK_ALSO];
+  if (nbad) {  // runs of mismatched blocks repaired in parallel, then whatever is left, in order
+    k_chain_fix_par<<<grid_for(nbad, 64), 64, 0, c->stream>>>(ub, uo, (uint32_t)wb, hard_end, fmt, w->entry, w->rel,
+                                                               w->count, w->exitp, badlist, nbad, mark);
+    HIPCHK(c, hipMemsetAsync(nbad_d, 0, 4, c->stream));
+    k_stitch_check<<<grid_for(wb - 1, 256), 256, 0, c->stream>>>(w->entry, w->exitp, (uint32_t)wb, nbad_d, badlist,
+                                                                 (uint32_t)wb, nullptr);
+    HIPCHK(c, hipMemcpyAsync(&nbad, nbad_d, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  if (nbad) {
+    // sort the mismatch list (atomic order is arbitrary)
+    std::vector<uint32_t> bl(nbad);
+    HIPCHK(c, copy_sync(c, bl.data(), badlist, nbad * 4, hipMemcpyDeviceToHost));
+    std::sort(bl.begin(), bl.end());
+    HIPCHK(c, copy_sync(c, badlist, bl.data(), nbad * 4, hipMemcpyHostToDevice));
+    k_chain_fix<<<1, 64, 0, c->stream>>>(ub, uo, (uint32_t)wb, hard_end, fmt, w->entry, w->rel, w->count, w->exitp,
+                                         badlist, nbad);
+    HIPCHK(c, hipGetLastError());
+  }
+  w->nrec = 0;
+  if ((rc = scan_exclusive<uint32_t>(c, w->count, wb, w->rbase, &w->nrec))) return rc;
+  if (last_exit) HIPCHK(c, copy_sync(c, last_exit, w->exitp + (wb - 1), 8, hipMemcpyDeviceToHost));
+  return HBAM_OK;
+}
+
 }  // namespace
 
 extern "C" int hbam_decode_split(hbam_ctx* c, const uint8_t* comp, int on_device,
@@ -1391,100 +1570,31 @@ extern "C" int hbam_decode_split(hbam_ctx* c, const uint8_t* comp, int on_device
   Chain ch;
   if ((rc = build_chain(c, d, comp_len, start, window_is_file_end, &ch))) return rc;
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-  BlockRec* blk = (BlockRec*)c->bufs[B_BLK].p;
-  uint64_t nb = ch.nb;
-
-  // ---- BCIS.seek(vStart): first block (empty -> the following one), offset checks
-  if (nb == 0) {
-    // readBlock at vStart's block fails (or EOF: count == 0 -> empty current block)
-    if (ch.end_code == HBAM_EEOF) {
-      // seek to a position at/after the end: empty block, offset must be 0 and eof
-      if (uoff_s != 0) { out->status = HBAM_EIO; return HBAM_OK; }
-      out->status = HBAM_OK;
-      return HBAM_OK;
-    }
-    out->status = ch.end_code == HBAM_ERUNTIMEIO ? HBAM_EIO : ch.end_code;
+  const uint64_t nb = ch.nb;
+  if (nb == 0) {  // readBlock at vStart's block fails, or finds the end of the file
+    out->status = bgzf_seek(0, ch.end_code, NO_BLOCK, HBAM_EEOF, nullptr, uoff_s, comp_base, file_len).status;
     return HBAM_OK;
   }
-  // blocks: table is device resident; ISIZE clamp + first oversized block
-  uint32_t* isz;
-  uint64_t* uoff;
-  uint64_t* small;
-  if ((rc = ensure(c, B_ISZ32, nb + 1, &isz))) return rc;
-  if ((rc = ensure(c, B_UOFF, nb + 1, &uoff))) return rc;
-  if ((rc = ensure(c, B_SMALL, 16, &small))) return rc;
-  HIPCHK(c, hipMemsetAsync(small, 0xff, 8 * 8, c->stream));
-  HIPCHK(c, hipMemsetAsync(small + 8, 0, 8 * 8, c->stream));
-  k_isize32<<<grid_for(nb, 256), 256, 0, c->stream>>>(blk, nb, isz, (uint32_t*)small);
-  if ((rc = scan_exclusive<uint32_t>(c, isz, nb, uoff, nullptr))) return rc;
-  // the inflated total and the first blocks (host view, for the seek semantics): one round trip
-  BlockRec b0[2];
-  HIPCHK(c, hipMemcpyAsync(c->pinned_small + 64, uoff + nb, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->pinned_small + 66, blk, std::min<uint64_t>(nb, 2) * sizeof(BlockRec),
-                           hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t utotal = c->pinned_small[64];
-  memcpy(b0, c->pinned_small + 66, std::min<uint64_t>(nb, 2) * sizeof(BlockRec));
-  // inflate
-  uint8_t* ub;
-  int32_t* st;
-  uint32_t* crc;
-  if ((rc = ensure(c, B_UBUF, utotal + UBUF_SLACK, &ub))) return rc;
-  if ((rc = ensure(c, B_INFST, nb + 1, &st))) return rc;
-  if ((rc = ensure(c, B_CRC, nb + 1, &crc))) return rc;
-  HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-  if ((rc = inflate_blocks(c, d, blk, nb, uoff, ub, st, c->opts.check_crc != 0, crc))) return rc;
-  HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
-  unsigned long long* first_bad = (unsigned long long*)small + 1;
-  k_first_bad_block<<<grid_for(nb, 256), 256, 0, c->stream>>>(st, crc, blk, nb, c->opts.check_crc,
-                                                             first_bad);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->pinned_small, small, 16, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  uint64_t fb = c->pinned_small[1];
-  const uint32_t bigi = (uint32_t)(c->pinned_small[0] & 0xffffffffu);
-  int32_t fb_code = HBAM_EEOF;
-  if (fb != ~0ULL) {
-    int32_t s;
-    HIPCHK(c, copy_sync(c, &s, st + fb, 4, hipMemcpyDeviceToHost));
-    fb_code = (s == INF_DATA) ? HBAM_EDATA : HBAM_EFORMAT;
+  // ---- blocks: sizes, inflate (all of them), the first that fails, BCIS.seek(vStart)
+  BgzfSplit bs;
+  if ((rc = bgzf_sizes(c, nb, 2, &bs))) return rc;
+  if ((rc = bgzf_inflate(c, d, nb, bs.utotal, c->opts.check_crc != 0, &bs))) return rc;
+  const SeekOutcome sk =
+      bgzf_seek(nb, ch.end_code, bs.fb, bs.fb_code, bs.hb.data(), uoff_s, comp_base, file_len);
+  if (sk.ends) {
+    out->status = sk.status;
+    return HBAM_OK;
   }
-  if (bigi != 0xffffffffu && (fb == ~0ULL || bigi < fb)) {
-    fb = bigi;
-    fb_code = HBAM_EUNSUPPORTED;
-  }
+  const uint64_t sblk = sk.sblk;
   // hard end: first failing block, else the chain end
   uint64_t hard_end;
   int32_t hard_code;
-  if (fb != ~0ULL) {
-    HIPCHK(c, copy_sync(c, &hard_end, uoff + fb, 8, hipMemcpyDeviceToHost));
-    hard_code = fb_code;
+  if (bs.fb != NO_BLOCK) {
+    HIPCHK(c, copy_sync(c, &hard_end, bs.uoff + bs.fb, 8, hipMemcpyDeviceToHost));
+    hard_code = bs.fb_code;
   } else {
-    hard_end = utotal;
+    hard_end = bs.utotal;
     hard_code = ch.end_code;
-  }
-  // seek: block 0 (or 1 if block 0 is empty)
-  uint64_t sblk = 0;
-  if (b0[0].isize == 0) {
-    if (fb == 0) { out->status = fb_code; return HBAM_OK; }
-    sblk = 1;
-  }
-  if (fb == sblk) { out->status = fb_code; return HBAM_OK; }
-  uint64_t r0;
-  if (sblk >= nb) {
-    // available() after an empty last block: EOF or readBlock error
-    if (ch.end_code != HBAM_EEOF) { out->status = ch.end_code == HBAM_ERUNTIMEIO ? HBAM_EIO : ch.end_code; return HBAM_OK; }
-    if (uoff_s != 0) { out->status = HBAM_EIO; return HBAM_OK; }
-    out->status = HBAM_OK;
-    return HBAM_OK;
-  }
-  {
-    const BlockRec& bs = b0[sblk];
-    const uint64_t after = comp_base + bs.coff + bs.clen;  // file position after the block
-    const bool eof = (after == file_len) || (file_len - after == 28);
-    if (uoff_s > bs.isize || (uoff_s == bs.isize && !eof)) { out->status = HBAM_EIO; return HBAM_OK; }
-    // uoff[sblk] is 0: sblk is 1 only when block 0 is empty (uoff[1] = ISIZE 0)
-    r0 = uoff_s;
   }
   // events: empty blocks after the seek block, at positions <= hard_end, in block order (so
   // sorted by position: k_decode_fixed binary-searches them; any number of them)
@@ -1493,73 +1603,29 @@ extern "C" int hbam_decode_split(hbam_ctx* c, const uint8_t* comp, int on_device
   uint64_t* evpos;
   const uint64_t nbs = nb - sblk;
   if ((rc = ensure(c, B_EVFLAG, nbs + 1, &evflag)) || (rc = ensure(c, B_EVPOS, nbs + 1, &evpos))) return rc;
-  k_empty_flags<<<grid_for(nbs, 256), 256, 0, c->stream>>>(blk + sblk, nbs, evflag);
+  k_empty_flags<<<grid_for(nbs, 256), 256, 0, c->stream>>>(bs.blk + sblk, nbs, evflag);
   HIPCHK(c, hipGetLastError());
   // their count is read back with the record walk's stitch count below (one round trip); the
   // list is sized for every block
   if ((rc = scan_exclusive(c, evflag, nbs, evpos, nullptr))) return rc;
   if ((rc = ensure(c, B_EVENTS, nbs + 1, &evd))) return rc;
-  k_empty_scatter<<<grid_for(nbs, 256), 256, 0, c->stream>>>(uoff + sblk, evflag, evpos, nbs, evd);
+  k_empty_scatter<<<grid_for(nbs, 256), 256, 0, c->stream>>>(bs.uoff + sblk, evflag, evpos, nbs, evd);
   HIPCHK(c, hipGetLastError());
   // events beyond the hard end cannot be reached; keep them (empty_at checks <= hard_end)
 
   // ---- K5: record starts (blocks [sblk, nb))
-  const uint64_t wb = nb - sblk;
-  const uint64_t* uo = uoff + sblk;
-  uint64_t *entry, *exitp, *rbase, *rec_off, *voff;
-  uint16_t* rel;
-  uint32_t *count, *badlist;
+  const uint64_t wb = nbs;
+  const uint64_t* uo = bs.uoff + sblk;
+  uint64_t *rec_off, *voff;
   HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
-  if ((rc = ensure(c, B_ENTRY, wb + 1, &entry))) return rc;
-  if ((rc = ensure(c, B_EXIT, wb + 1, &exitp))) return rc;
-  if ((rc = ensure(c, B_REL, wb * WALK_CAP, &rel))) return rc;
-  if ((rc = ensure(c, B_COUNT, wb + 1, &count))) return rc;
-  if ((rc = ensure(c, B_RECBASE, wb + 1, &rbase))) return rc;
-  if ((rc = ensure(c, B_BADLIST, wb + 1, &badlist))) return rc;
-  if (wb > 1)
-    k_block_entry<<<(uint32_t)(wb - 1), 64, 0, c->stream>>>(ub, uo, (uint32_t)wb, hard_end, BamFmt{n_ref},
-                                                            entry);
-  k_block_walk<<<grid_for(wb, 64), 64, 0, c->stream>>>(ub, uo, (uint32_t)wb, r0, hard_end, BamFmt{n_ref},
-                                                       entry, rel, count, exitp);
-  uint32_t* nbad_d = (uint32_t*)(small + 5);
-  uint8_t* mark;
-  if ((rc = ensure(c, B_MARK, wb + 1, &mark))) return rc;
-  HIPCHK(c, hipMemsetAsync(nbad_d, 0, 4, c->stream));
-  HIPCHK(c, hipMemsetAsync(mark, 0, 1, c->stream));  // block 0 (the split start) is never listed
-  if (wb > 1)
-    k_stitch_check<<<grid_for(wb - 1, 256), 256, 0, c->stream>>>(entry, exitp, (uint32_t)wb, nbad_d,
-                                                                 badlist, (uint32_t)wb, mark);
-  HIPCHK(c, hipMemcpyAsync(c->pinned_small + 80, nbad_d, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->pinned_small + 81, evpos + nbs, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  uint32_t nbad = (uint32_t)c->pinned_small[80];
-  const uint64_t nev64 = c->pinned_small[81];
-  if (nev64 > 0xffffffffull) return set_err(c, HBAM_EUNSUPPORTED, "more than 2^32-1 empty BGZF blocks");
-  const uint32_t nev = (uint32_t)nev64;
-  if (nbad) {  // runs of mismatched blocks repaired in parallel, then whatever is left, in order
-    k_chain_fix_par<<<grid_for(nbad, 64), 64, 0, c->stream>>>(ub, uo, (uint32_t)wb, hard_end, BamFmt{n_ref},
-                                                               entry, rel, count, exitp, badlist, nbad, mark);
-    HIPCHK(c, hipMemsetAsync(nbad_d, 0, 4, c->stream));
-    k_stitch_check<<<grid_for(wb - 1, 256), 256, 0, c->stream>>>(entry, exitp, (uint32_t)wb, nbad_d,
-                                                                 badlist, (uint32_t)wb, nullptr);
-    HIPCHK(c, hipMemcpyAsync(&nbad, nbad_d, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  if (nbad) {
-    // sort the mismatch list (atomic order is arbitrary)
-    std::vector<uint32_t> bl(nbad);
-    HIPCHK(c, copy_sync(c, bl.data(), badlist, nbad * 4, hipMemcpyDeviceToHost));
-    std::sort(bl.begin(), bl.end());
-    HIPCHK(c, copy_sync(c, badlist, bl.data(), nbad * 4, hipMemcpyHostToDevice));
-    k_chain_fix<<<1, 64, 0, c->stream>>>(ub, uo, (uint32_t)wb, hard_end, BamFmt{n_ref}, entry, rel, count,
-                                         exitp, badlist, nbad);
-    HIPCHK(c, hipGetLastError());
-  }
-  uint64_t nrec = 0;
-  if ((rc = scan_exclusive<uint32_t>(c, count, wb, rbase, &nrec))) return rc;
+  ChainWalk w;
+  if ((rc = walk_chain(c, bs.ub, uo, wb, sk.r0, hard_end, BamFmt{n_ref}, &w, evpos + nbs))) return rc;
+  if (w.also > 0xffffffffull) return set_err(c, HBAM_EUNSUPPORTED, "more than 2^32-1 empty BGZF blocks");
+  const uint32_t nev = (uint32_t)w.also;
+  const uint64_t nrec = w.nrec;
   if ((rc = ensure(c, B_RECOFF, nrec + 1, &rec_off))) return rc;
   if ((rc = ensure(c, B_VOFF, nrec + 1, &voff))) return rc;
-  k_emit_offsets<<<(uint32_t)wb, 256, 0, c->stream>>>(uo, blk + sblk, (uint32_t)wb, rel, count, rbase,
+  k_emit_offsets<<<(uint32_t)wb, 256, 0, c->stream>>>(uo, bs.blk + sblk, (uint32_t)wb, w.rel, w.count, w.rbase,
                                                       comp_base, rec_off, voff);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
@@ -1567,11 +1633,11 @@ extern "C" int hbam_decode_split(hbam_ctx* c, const uint8_t* comp, int on_device
   // ---- K6/K7/K8
   DevColumns dc{};
   if ((rc = fill_columns(c, nrec, &dc))) return rc;
-  unsigned long long* first_stop = (unsigned long long*)small + 6;
+  unsigned long long* first_stop = (unsigned long long*)bs.small + SM_FIRST_STOP;
   HIPCHK(c, hipMemsetAsync(first_stop, 0xff, 8, c->stream));
   if (nrec)
     k_decode_fixed<<<grid_for(nrec, 256), 256, 0, c->stream>>>(
-        ub, nrec, rec_off, voff, v_end, hard_end, hard_code, evd, nev, n_ref, c->opts.validate_refs,
+        bs.ub, nrec, rec_off, voff, v_end, hard_end, hard_code, evd, nev, n_ref, c->opts.validate_refs,
         dc, first_stop);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
@@ -1602,8 +1668,8 @@ extern "C" int hbam_decode_split(hbam_ctx* c, const uint8_t* comp, int on_device
     if (n_final >= nrec) HIPCHK(c, copy_sync(c, voff + n_final, &v_start, 8, hipMemcpyHostToDevice));
   }
   // ---- pools
-  if ((rc = finish_pools(c, ub, n_final, rec_off, dc))) return rc;
-  columns_out(out, dc, voff, rec_off, ub, utotal, n_final, status, err_rec);
+  if ((rc = finish_pools(c, bs.ub, n_final, rec_off, dc))) return rc;
+  columns_out(out, dc, voff, rec_off, bs.ub, bs.utotal, n_final, status, err_rec);
 
   c->timing.scan_ms = ev_ms(c, 0, 1);
   c->timing.inflate_ms = ev_ms(c, 2, 3);
@@ -1614,7 +1680,7 @@ extern "C" int hbam_decode_split(hbam_ctx* c, const uint8_t* comp, int on_device
   c->timing.total_ms = ev_ms(c, 0, 8);
   c->timing.n_blocks = nb;
   c->timing.comp_bytes = ch.end_pos - start;
-  c->timing.ubuf_bytes = utotal;
+  c->timing.ubuf_bytes = bs.utotal;
   c->timing.n_records = n_final;
   return HBAM_OK;
 }
