@@ -2262,7 +2262,10 @@ int guess_run(hbam_ctx* c, const uint64_t* wptr, const int64_t* wlen, const int6
   // Initial ByteBuffer of BAMSplitGuesser(ss, conf): the ctor reads the file magic into it
   // (:85-87) and throws unless it is 1f 8b 08 04.  Only windows shorter than 4 bytes could
   // observe a stale buffer carried over from a previous guess, and those always return `end`
-  // (the XLEN seek at p0+10 fails), so guesses are independent.
+  // (the XLEN seek at p0+10 fails), so guesses are independent.  A longer window's first read
+  // fills all four bytes; the short reads at its end (a window that stops one to three bytes
+  // into a magic, tests/guess_cases.py family D) leave bytes of the same guess's earlier reads,
+  // which the kernel reproduces from the window alone.
   const uint8_t magic[8] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0};
   HIPCHK(c, hipEventRecord(c->ev[9], c->stream));
   uint64_t batch = c->guess_batch;

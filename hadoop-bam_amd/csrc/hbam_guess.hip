@@ -104,7 +104,11 @@ __device__ int32_t gb_read_block(GBcis& b, GStream& f) {
   if (!(h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && h[3] == 4)) return HBAM_EFORMAT;
   if ((h[10] | h[11] << 8) != 6) return HBAM_EFORMAT;
   if (blen < 26) return HBAM_EDATA;
-  if (isize > 65536) return HBAM_EUNSUPPORTED;
+  // htsjdk inflates into an ISIZE-byte array: with ISIZE > 65536 a stream that ends short of it is
+  // "Did not inflate expected amount" (SAMFormatException, which the guess loop skips) and a corrupt
+  // one the inflater's error.  Only a stream that really holds 65536 bytes or more is beyond this
+  // reader (no cache entry has such an ISIZE: the in-lane branch below decides).
+  const bool big = isize > 65536;
   const uint32_t expect = (uint32_t)h[blen - 8] | (uint32_t)h[blen - 7] << 8 |
                           (uint32_t)h[blen - 6] << 16 | (uint32_t)h[blen - 5] << 24;
   // cache lookup (binary search over the window's sorted candidates)
@@ -128,10 +132,11 @@ __device__ int32_t gb_read_block(GBcis& b, GStream& f) {
     b.cur = b.cache.ubuf + b.cache.uoff[hit];
   } else {
     uint32_t produced = 0;
-    const int32_t st = inflate_raw(h + 18, (uint32_t)(blen - 26), b.scratch, (uint32_t)isize, b.s_ll,
-                                   b.s_d, b.lens, &produced);
+    const int32_t st = inflate_raw(h + 18, (uint32_t)(blen - 26), b.scratch, big ? 65536u : (uint32_t)isize,
+                                   b.s_ll, b.s_d, b.lens, &produced);
     if (st == INF_DATA) return HBAM_EDATA;
     if (st == INF_SHORT) return HBAM_EFORMAT;
+    if (big) return HBAM_EUNSUPPORTED;
     if (b.check_crc) {
       uint32_t c = 0xffffffffu;
       for (int32_t i = 0; i < isize; ++i) c = b.crc_tab[(c ^ b.scratch[i]) & 0xff] ^ (c >> 8);
@@ -469,8 +474,10 @@ __device__ void crc_table_init(uint32_t* T) {
 //   * guessNextBGZFPos' magic scan (:229-247): the window's magic positions in [0, firstEnd]
 //     are listed once by 64 lanes; the scan's result from p is the first listed position q >= p
 //     with q < firstEnd or q == p (the skip rule never steps over a magic, and the end test
-//     only follows an advance).  Windows shorter than firstEnd + 4 (where a 4-byte read can be
-//     short and leave stale bytes in `buf`) take the lane-serial path.
+//     only follows an advance; from p > firstEnd, reached through p = p0 + 4 behind a false
+//     magic, only q == p is left, and the bytes at p are read instead of the list).  Windows
+//     shorter than firstEnd + 4 (where a 4-byte read can be short and leave stale bytes in
+//     `buf`) take the lane-serial path.
 //   * guessNextBAMPos' candidate loop (:301-398): bam_pred() is the loop's test as a pure
 //     function of the inflated block (every read lies inside it), evaluated for 64 offsets at
 //     a time.  The serial g_next_bam is then run on the accepted offset (or the last one
@@ -506,15 +513,26 @@ __device__ bool g_next_bgzf_listed(Guesser& g, int32_t p, int32_t end, const int
                                    uint32_t nmag, int32_t* opos, int32_t* osize) {
   for (;;) {
     if (!gs_seek(g.in, p)) return false;
-    uint32_t lo = 0, hi = nmag;  // first listed position >= p
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (mag[mid] < p) lo = mid + 1;
-      else hi = mid;
+    int32_t q;
+    if (p > end) {
+      // past the listed range [0, end]: the scan can stand here after p = p0 + 4 (or cp = a block
+      // found that way, + 1), and its first read comes before any end test, so a magic at p itself
+      // is found; anything else advances and leaves by p >= end.  A short read cannot match
+      // either way: the XLEN seek at p + 10 then leaves the window.
+      const uint8_t* a = g.in.a + p;
+      if (g.in.len - p < 4 || !(a[0] == 0x1f && a[1] == 0x8b && a[2] == 8 && a[3] == 4)) return false;
+      q = p;
+    } else {
+      uint32_t lo = 0, hi = nmag;  // first listed position >= p
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (mag[mid] < p) lo = mid + 1;
+        else hi = mid;
+      }
+      if (lo == nmag) return false;
+      q = mag[lo];
+      if (q != p && q >= end) return false;
     }
-    if (lo == nmag) return false;
-    const int32_t q = mag[lo];
-    if (q != p && q >= end) return false;
     p = q;
     gs_seek(g.in, p);
     gs_read(g.in, g.buf, 4);  // the read that matched: buf = the magic, pos = p + 4
