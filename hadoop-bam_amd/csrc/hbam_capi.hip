@@ -2997,6 +2997,7 @@ extern "C" int64_t hbam_bgzf_compress(hbam_ctx* c, const uint8_t* src, int src_o
 #include "hbam_lines.hip"
 #include "hbam_vcf.hip"
 #include "hbam_sam.hip"
+#include "hbam_textout.hip"
 #include "hbam_samtext.hip"
 #include "hbam_fastq.hip"
 #include "hbam_fasta.hip"

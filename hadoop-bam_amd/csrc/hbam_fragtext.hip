@@ -1,22 +1,20 @@
 // hbam_fragtext.hip — FASTQ and QSEQ text out of the device: FastqRecordWriter.write and
 // QseqRecordWriter.write over hbam_frag_columns (FastqOutputFormat, QseqOutputFormat), the inverse
-// of hbam_fastq.hip.  Included at the end of hbam_capi.hip, after hbam_fastq.hip.  gfx950, wave64.
-// The shape is hbam_samtext.hip's:
+// of hbam_fastq.hip.  Included at the end of hbam_capi.hip, after hbam_fastq.hip, over the host
+// sequence of hbam_textout.hip (no deferred records).  gfx950, wave64.
 //
 //   k_fragtext_sizes   a lane per output record: the record's fields gathered from the columns
 //                      (frag_text_load) and its text counted by frag_text (frag_text.h) in its
 //                      counting mode: offsets, the present mask and the digit counts, no pool or
 //                      window byte.  It leaves the bulk pass's descriptor, and stops the output at
 //                      a record whose offsets or string pairs cannot be followed (HBAM_EINVAL).
-//   (scan_exclusive)   lengths -> line_off
+//   (textout_layout)   lengths -> line_off
 //   k_fragtext_head    a lane per record: the same frag_text with an output pointer writes the id
 //                      line or the eight leading QSEQ fields and what follows the quality, four
 //                      bytes per store (SamOut)
-//   k_fragtext_bulk    sequence, separator, quality: nearly all of the text.  As k_samtext_bulk, a
-//                      wave takes a tile of 64 records, cuts each record's region into 16-byte units
-//                      aligned in the OUTPUT, numbers the units with a wave scan and gives them to
-//                      consecutive lanes, so a wave store covers 1 KiB of consecutive text and a
-//                      10,000-base read is the whole wave's work.  frag_text_unit applies 'N' -> '.'
+//   k_fragtext_bulk    sequence, separator, quality: nearly all of the text.  As k_samtext_bulk
+//                      (unit_tiles.h), each record's region is cut into 16-byte units aligned in
+//                      the OUTPUT.  frag_text_unit applies 'N' -> '.'
 //                      and + 31 and checks the unit's bytes; a bad byte marks its record and the
 //                      first such record (atomicMin) ends the output.
 //
@@ -78,64 +76,47 @@ __global__ __launch_bounds__(FRAGTEXT_WG) void k_fragtext_bulk(const uint8_t* __
                                                                uint32_t sep, uint32_t mode,
                                                                uint8_t* __restrict__ text, uint32_t* __restrict__ bad,
                                                                unsigned long long* first_stop) {
-  __shared__ uint32_t s_excl[FRAGTEXT_WG / 64][64];
   __shared__ uint4 s_len[FRAGTEXT_WG / 64][64];   // ls, lq, R lo, R hi
   __shared__ uint4 s_src[FRAGTEXT_WG / 64][64];   // seq offset lo, hi, qual offset lo, hi
-  const uint32_t lane = threadIdx.x & 63u;
-  uint32_t* const ex = s_excl[threadIdx.x >> 6];
   uint4* const sl = s_len[threadIdx.x >> 6];
   uint4* const ss = s_src[threadIdx.x >> 6];
-  const uint32_t ntiles = (n + 63u) / 64u;
-  const uint32_t wstride = gridDim.x * (FRAGTEXT_WG / 64);
-  for (uint32_t t = blockIdx.x * (FRAGTEXT_WG / 64) + (threadIdx.x >> 6); t < ntiles; t += wstride) {
-    const uint32_t line = t * 64u + lane;
-    uint4 d0 = make_uint4(0, 0, 0, 0), d1 = make_uint4(0, 0, 0, 0);
-    uint64_t R = 0;
-    uint32_t blen = 0;
-    if (line < n) {
-      d0 = desc[2 * (uint64_t)line];
-      d1 = desc[2 * (uint64_t)line + 1];
-      R = line_off[line] + d0.z;
-      blen = d0.x + sep + d0.y;
-    }
-    const uint32_t units = sam_text_units(R, blen);
-    const uint32_t incl = wave_scan_dpp(units), T = wave_last(incl);
-    if (T == 0u) continue;  // wave-uniform
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");  // the previous tile's reads of ex / sl / ss precede these writes
-    ex[lane] = incl - units;
-    sl[lane] = make_uint4(d0.x, d0.y, (uint32_t)R, (uint32_t)(R >> 32));
-    ss[lane] = d1;
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");  // (one wave: its LDS operations run in issue order)
-    for (uint32_t q0 = 0; q0 < T; q0 += 64u) {
-      const uint32_t q = q0 + lane;
-      if (q >= T) continue;
-      // the last record whose first unit is <= q (ex[0] = 0; records without units tie with the next one)
-      uint32_t r = 0, hi = 63;
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        const uint32_t mid = (r + hi + 1u) >> 1;
-        if (ex[mid] <= q) r = mid;
-        else hi = mid - 1u;
-      }
-      const uint4 L = sl[r], S = ss[r];
-      const uint64_t Rr = (uint64_t)L.z | (uint64_t)L.w << 32;
-      uint32_t p0, nb, o[4];
-      sam_text_unit_span(Rr, L.x + sep + L.y, q - ex[r], &p0, &nb);
-      const uint32_t f = frag_text_unit(seq + ((uint64_t)S.x | (uint64_t)S.y << 32), L.x,
-                                        qual + ((uint64_t)S.z | (uint64_t)S.w << 32), sep, mode, p0, nb, o);
-      const u32x4_a1 v = u32x4_a1{o[0], o[1], o[2], o[3]};
-      HBAM_G uint8_t* const gd = (HBAM_G uint8_t*)(text + Rr + p0);
-      if (nb >= 16u) *(HBAM_G u32x4_a1*)gd = v;
-      else st_part_g(gd, nb, v);
-      if (f) {
-        const uint32_t at = t * 64u + r;
-        atomicOr(bad + at, f);
-        atomicMin(first_stop, (unsigned long long)at);
-      }
-    }
-  }
+  uint4 d0, d1;
+  uint64_t R;
+  unit_tiles<FRAGTEXT_WG>(
+      n,
+      [&](uint32_t line) {
+        d0 = d1 = make_uint4(0, 0, 0, 0);
+        R = 0;
+        uint32_t blen = 0;
+        if (line < n) {
+          d0 = desc[2 * (uint64_t)line];
+          d1 = desc[2 * (uint64_t)line + 1];
+          R = line_off[line] + d0.z;
+          blen = d0.x + sep + d0.y;
+        }
+        return sam_text_units(R, blen);
+      },
+      [&](uint32_t lane) {
+        sl[lane] = make_uint4(d0.x, d0.y, (uint32_t)R, (uint32_t)(R >> 32));
+        ss[lane] = d1;
+      },
+      [&](uint32_t t, uint32_t r, uint32_t k) {
+        const uint4 L = sl[r], S = ss[r];
+        const uint64_t Rr = (uint64_t)L.z | (uint64_t)L.w << 32;
+        uint32_t p0, nb, o[4];
+        sam_text_unit_span(Rr, L.x + sep + L.y, k, &p0, &nb);
+        const uint32_t f = frag_text_unit(seq + ((uint64_t)S.x | (uint64_t)S.y << 32), L.x,
+                                          qual + ((uint64_t)S.z | (uint64_t)S.w << 32), sep, mode, p0, nb, o);
+        const u32x4_a1 v = u32x4_a1{o[0], o[1], o[2], o[3]};
+        HBAM_G uint8_t* const gd = (HBAM_G uint8_t*)(text + Rr + p0);
+        if (nb >= 16u) *(HBAM_G u32x4_a1*)gd = v;
+        else st_part_g(gd, nb, v);
+        if (f) {
+          const uint32_t at = t * 64u + r;
+          atomicOr(bad + at, f);
+          atomicMin(first_stop, (unsigned long long)at);
+        }
+      });
 }
 
 }  // namespace hbam
@@ -273,77 +254,50 @@ extern "C" int hbam_frag_render(hbam_ctx* c, const hbam_frag_columns* cols, cons
     if (window_len) HIPCHK(c, hipMemcpyAsync(dwin, window, window_len, hipMemcpyHostToDevice, c->stream));
     in.window = dwin;
   }
-  uint32_t *len, *bad;
+  TextOut T{{B_FT_LEN, B_FT_BAD, B_FT_LINEOFF, B_FT_SMALL, B_FT_TEXT, false}};
   uint4* desc;
-  uint64_t *line_off, *small;
-  if ((rc = ensure(c, B_FT_LEN, n + 1, &len)) || (rc = ensure(c, B_FT_BAD, n + 1, &bad)) ||
-      (rc = ensure(c, B_FT_DESC, 2 * n + 2, &desc)) || (rc = ensure(c, B_FT_LINEOFF, n + 1, &line_off)) ||
-      (rc = ensure(c, B_FT_SMALL, 2, &small)))
-    return rc;
-  unsigned long long* first_stop = (unsigned long long*)small;
-  HIPCHK(c, hipMemsetAsync(small, 0xff, 8, c->stream));
-  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+  if ((rc = ensure(c, B_FT_DESC, 2 * n + 2, &desc)) || (rc = textout_begin(c, n, &T))) return rc;
+  uint32_t* const bad = (uint32_t*)T.lstatus;  // FRAG_BAD_* bits, not a status
   if (n)
-    k_fragtext_sizes<<<grid_for(n, FRAGTEXT_WG), FRAGTEXT_WG, 0, c->stream>>>(in, perm, (uint32_t)n, format, flags, len,
-                                                                            bad, desc, first_stop);
+    k_fragtext_sizes<<<grid_for(n, FRAGTEXT_WG), FRAGTEXT_WG, 0, c->stream>>>(in, perm, (uint32_t)n, format, flags,
+                                                                            T.len, bad, desc, T.first_stop);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->pinned_small + 8, small, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  uint64_t m = n;  // the records that stand
-  int32_t status = HBAM_OK;
-  if (c->pinned_small[8] < n) {
-    m = c->pinned_small[8];
-    status = HBAM_EINVAL;
-  }
-  uint64_t text_len = 0, partial_len = 0;
-  if ((rc = scan_exclusive<uint32_t>(c, len, m, line_off, &text_len))) return rc;
-  uint8_t* text;
-  if ((rc = ensure(c, B_FT_TEXT, text_len + 64, &text))) return rc;
-  HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-  if (m)
-    k_fragtext_head<<<grid_for(m, FRAGTEXT_WG), FRAGTEXT_WG, 0, c->stream>>>(in, perm, (uint32_t)m, format, flags,
-                                                                           line_off, text);
+  if ((rc = textout_stop(c, &T))) return rc;
+  if (T.cut) T.status = HBAM_EINVAL;  // the sizes pass has one reason to stop
+  if ((rc = textout_layout(c, &T))) return rc;
+  if (T.m)
+    k_fragtext_head<<<grid_for(T.m, FRAGTEXT_WG), FRAGTEXT_WG, 0, c->stream>>>(in, perm, (uint32_t)T.m, format, flags,
+                                                                             T.line_off, T.text);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-  HIPCHK(c, hipMemsetAsync(small, 0xff, 8, c->stream));
+  if ((rc = textout_arm(c, T))) return rc;
   const uint32_t sep = format == HBAM_FRAG_FASTQ ? FRAG_SEP_FASTQ : FRAG_SEP_QSEQ;
   const uint32_t mode = (format == HBAM_FRAG_QSEQ ? FRAG_MODE_QSEQ : 0u) |
                         (encoding == HBAM_QUAL_ILLUMINA ? FRAG_MODE_ILLUMINA : 0u);
-  if (m)
-    k_fragtext_bulk<<<(uint32_t)std::min<uint64_t>(grid_for(m, FRAGTEXT_WG), POOLS_MAX_WG), FRAGTEXT_WG, 0,
-                      c->stream>>>(in.seq, in.qual, desc, line_off, (uint32_t)m, sep, mode, text, bad, first_stop);
+  if (T.m)
+    k_fragtext_bulk<<<(uint32_t)std::min<uint64_t>(grid_for(T.m, FRAGTEXT_WG), POOLS_MAX_WG), FRAGTEXT_WG, 0,
+                      c->stream>>>(in.seq, in.qual, desc, T.line_off, (uint32_t)T.m, sep, mode, T.text, bad,
+                                   T.first_stop);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->pinned_small + 8, small, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->pinned_small[8] < m) {  // a byte of the sequence or the quality: the records before that one stand
-    m = c->pinned_small[8];
+  if ((rc = textout_stop(c, &T))) return rc;
+  if (T.cut) {  // a byte of the sequence or the quality: the records before that one stand
     uint32_t f = 0;
     uint64_t lo[2];
     uint4 d0;
-    HIPCHK(c, copy_sync(c, &f, bad + m, 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, copy_sync(c, lo, line_off + m, 16, hipMemcpyDeviceToHost));
-    HIPCHK(c, copy_sync(c, &d0, desc + 2 * m, 16, hipMemcpyDeviceToHost));
-    text_len = lo[0];
+    HIPCHK(c, copy_sync(c, &f, bad + T.m, 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, copy_sync(c, lo, T.line_off + T.m, 16, hipMemcpyDeviceToHost));
+    HIPCHK(c, copy_sync(c, &d0, desc + 2 * T.m, 16, hipMemcpyDeviceToHost));
+    T.text_len = lo[0];
     if (format == HBAM_FRAG_QSEQ) {
-      status = (f & FRAG_BAD_BYTE) ? HBAM_EUNSUPPORTED : HBAM_ERUNTIME;
+      T.status = (f & FRAG_BAD_BYTE) ? HBAM_EUNSUPPORTED : HBAM_ERUNTIME;
     } else {
-      status = HBAM_ESEQFORMAT;
-      partial_len = lo[1] - lo[0] - d0.y - 1;  // "@id\nseq\n+\n": the stream holds it when convertQuality throws
+      T.status = HBAM_ESEQFORMAT;
+      // "@id\nseq\n+\n", the record without its quality (d0.y) and last '\n': the stream holds it when
+      // convertQuality throws
+      out->partial_len = lo[1] - lo[0] - d0.y - 1;
     }
   }
-  out->n_records = m;
-  out->status = status;
-  out->err_record = status ? m : 0;
-  out->text_len = text_len;
-  out->partial_len = partial_len;
-  out->text = text;
-  out->line_off = line_off;
-  c->timing.walk_ms = ev_ms(c, 0, 1);
-  c->timing.huffman_ms = ev_ms(c, 1, 2);
-  c->timing.resolve_ms = ev_ms(c, 2, 3);
-  c->timing.total_ms = ev_ms(c, 0, 3);
-  c->timing.n_records = m;
-  c->timing.ubuf_bytes = text_len;
+  textout_finish(c, T, out);  // (partial_len stays)
   return HBAM_OK;
 }

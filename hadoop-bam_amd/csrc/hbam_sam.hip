@@ -17,18 +17,17 @@
 //   k_sam_encode       a lane per line: the fixed fields, name, CIGAR and aux written at rec_off, and
 //                      the line's SEQ / QUAL descriptor for the bulk pass
 //   k_sam_bulk         SEQ and QUAL, about two thirds of the text, the way k_decode_pools moves
-//                      pools: a wave takes a tile of 64 lines, cuts their packed SEQ and their QUAL
-//                      into 16-byte output units, numbers the units with a wave scan and gives them
-//                      to consecutive lanes, so a wave store covers 1 KiB of consecutive record bytes
-//                      and a 6 KB long-read line is the whole wave's work.  A SEQ unit reads 32
-//                      characters (two unaligned 16-byte loads), a QUAL unit 16.  A byte outside
-//                      the SEQ table or a QUAL byte below '!' stops the split at that line.
+//                      pools: the lines' packed SEQ and QUAL cut into 16-byte output units and given
+//                      to consecutive lanes (unit_tiles.h).  A SEQ unit reads 32 characters (two
+//                      unaligned 16-byte loads), a QUAL unit 16.  A byte outside the SEQ table or a
+//                      QUAL byte below '!' stops the split at that line.
 //   k_sam_keys         the key of the records that are not placed (BAMRecordReader.getKey :88-95):
 //                      k_decode_fixed hashes the raw variable block, which a SAM record does not have
 //
 // Loads past a field stay inside the 64 readable bytes behind the window (include/hbam.h).
 
 #include "sam_line.h"
+#include "unit_tiles.h"
 
 namespace hbam {
 
@@ -91,75 +90,54 @@ __global__ __launch_bounds__(SAM_WG) void k_sam_bulk(const uint8_t* __restrict__
                                                      const uint4* __restrict__ desc, uint32_t n,
                                                      uint8_t* __restrict__ ub, int32_t* __restrict__ status,
                                                      unsigned long long* first_stop) {
-  __shared__ uint32_t s_excl[SAM_WG / 64][64];
   __shared__ uint4 s_desc[SAM_WG / 64][64];
-  const uint32_t lane = threadIdx.x & 63u;
-  uint32_t* const ex = s_excl[threadIdx.x >> 6];
   uint4* const sd = s_desc[threadIdx.x >> 6];
-  const uint32_t ntiles = (n + 63u) / 64u;
-  const uint32_t wstride = gridDim.x * (SAM_WG / 64);
-  for (uint32_t t = blockIdx.x * (SAM_WG / 64) + (threadIdx.x >> 6); t < ntiles; t += wstride) {
-    const uint32_t line = t * 64u + lane;
-    const uint4 d = line < n ? desc[line] : make_uint4(0, 0, 0, 0);
-    const uint32_t lseq = d.y & 0x7fffffffu;
-    const uint32_t units = ((lseq + 1u) / 2u + 15u) / 16u + (lseq + 15u) / 16u;
-    const uint32_t incl = wave_scan_dpp(units), T = wave_last(incl);
-    if (T == 0u) continue;  // wave-uniform
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");  // the previous tile's reads of ex / sd precede these writes
-    ex[lane] = incl - units;
-    sd[lane] = d;
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");  // (one wave: its LDS operations run in issue order)
-    for (uint32_t q0 = 0; q0 < T; q0 += 64u) {
-      const uint32_t q = q0 + lane;
-      if (q >= T) continue;
-      // the last line whose first unit is <= q (ex[0] = 0; lines without units tie with the next one)
-      uint32_t r = 0, hi = 63;
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        const uint32_t mid = (r + hi + 1u) >> 1;
-        if (ex[mid] <= q) r = mid;
-        else hi = mid - 1u;
-      }
-      const uint4 D = sd[r];
-      const uint32_t k = q - ex[r];
-      const uint32_t ls = D.y & 0x7fffffffu, packed = (ls + 1u) / 2u, us = (packed + 15u) / 16u;
-      const uint8_t* const src = text + D.x;
-      uint8_t* dst = ub + ((uint64_t)D.z | (uint64_t)D.w << 32);
-      uint32_t o[4], nbytes;
-      bool ok = true;
-      if (k < us) {
-        const uint32_t nchar = min(32u, ls - 32u * k);
-        const u32x4_a1 a = *(const HBAM_G u32x4_a1*)(src + 32u * k);
-        const u32x4_a1 b = *(const HBAM_G u32x4_a1*)(src + 32u * k + 16u);
-        const uint32_t w[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-        ok = sam_seq_unit(w, nchar, o);
-        nbytes = (nchar + 1u) / 2u;
-        dst += 16u * k;
-      } else {
-        const uint32_t kq = k - us;
-        nbytes = min(16u, ls - 16u * kq);
-        dst += packed + 16u * kq;
-        if (D.y >> 31) {
-          o[0] = o[1] = o[2] = o[3] = 0xffffffffu;
+  uint4 d;
+  unit_tiles<SAM_WG>(
+      n,
+      [&](uint32_t line) {
+        d = line < n ? desc[line] : make_uint4(0, 0, 0, 0);
+        const uint32_t lseq = d.y & 0x7fffffffu;
+        return ((lseq + 1u) / 2u + 15u) / 16u + (lseq + 15u) / 16u;
+      },
+      [&](uint32_t lane) { sd[lane] = d; },
+      [&](uint32_t t, uint32_t r, uint32_t k) {
+        const uint4 D = sd[r];
+        const uint32_t ls = D.y & 0x7fffffffu, packed = (ls + 1u) / 2u, us = (packed + 15u) / 16u;
+        const uint8_t* const src = text + D.x;
+        uint8_t* dst = ub + ((uint64_t)D.z | (uint64_t)D.w << 32);
+        uint32_t o[4], nbytes;
+        bool ok = true;
+        if (k < us) {
+          const uint32_t nchar = min(32u, ls - 32u * k);
+          const u32x4_a1 a = *(const HBAM_G u32x4_a1*)(src + 32u * k);
+          const u32x4_a1 b = *(const HBAM_G u32x4_a1*)(src + 32u * k + 16u);
+          const uint32_t w[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+          ok = sam_seq_unit(w, nchar, o);
+          nbytes = (nchar + 1u) / 2u;
+          dst += 16u * k;
         } else {
-          const u32x4_a1 a = *(const HBAM_G u32x4_a1*)(src + ls + 1u + 16u * kq);
-          const uint32_t w[4] = {a[0], a[1], a[2], a[3]};
-          ok = sam_qual_unit(w, nbytes, o);
+          const uint32_t kq = k - us;
+          nbytes = min(16u, ls - 16u * kq);
+          dst += packed + 16u * kq;
+          if (D.y >> 31) {
+            o[0] = o[1] = o[2] = o[3] = 0xffffffffu;
+          } else {
+            const u32x4_a1 a = *(const HBAM_G u32x4_a1*)(src + ls + 1u + 16u * kq);
+            const uint32_t w[4] = {a[0], a[1], a[2], a[3]};
+            ok = sam_qual_unit(w, nbytes, o);
+          }
         }
-      }
-      const u32x4_a1 v = u32x4_a1{o[0], o[1], o[2], o[3]};
-      HBAM_G uint8_t* const gd = (HBAM_G uint8_t*)dst;
-      if (nbytes >= 16u) *(HBAM_G u32x4_a1*)gd = v;
-      else st_part_g(gd, nbytes, v);
-      if (!ok) {
-        const uint32_t bad = t * 64u + r;
-        status[bad] = HBAM_EFORMAT;
-        atomicMin(first_stop, (unsigned long long)bad);
-      }
-    }
-  }
+        const u32x4_a1 v = u32x4_a1{o[0], o[1], o[2], o[3]};
+        HBAM_G uint8_t* const gd = (HBAM_G uint8_t*)dst;
+        if (nbytes >= 16u) *(HBAM_G u32x4_a1*)gd = v;
+        else st_part_g(gd, nbytes, v);
+        if (!ok) {
+          const uint32_t bad = t * 64u + r;
+          status[bad] = HBAM_EFORMAT;
+          atomicMin(first_stop, (unsigned long long)bad);
+        }
+      });
 }
 
 // key[i] of the records k_decode_fixed gave the raw-bytes hash: the chained hash of the read name

@@ -1,6 +1,7 @@
 // hbam_samtext.hip — SAM text out of the device: SAMTextWriter.writeAlignment over packed BAM
 // records (SAMRecordWriter, AnySAMOutputFormat's SAM half, the View plugin), the inverse of
-// hbam_sam.hip.  Included at the end of hbam_capi.hip, after hbam_sam.hip.  gfx950, wave64.
+// hbam_sam.hip.  Included at the end of hbam_capi.hip, after hbam_sam.hip and hbam_textout.hip (the
+// host sequence the three text writers share).  gfx950, wave64.
 //
 //   k_samtext_sizes    a lane per output line: the record rendered by sam_text (sam_text.h) in its
 //                      counting mode for the line's length, its status, whether the host has to
@@ -9,17 +10,14 @@
 //                      quality byte; the other bytes come through the 16-byte register cache
 //                      (SamRecBytes), since a lane per record pays a cache line per lane for every
 //                      load instruction whatever its width.
-//   (scan_exclusive)   lengths -> line_off; deferred flags -> their ranks, k_samtext_deferred
-//                      compacts the deferred output positions, ascending
+//   (textout_layout)   lengths -> line_off; deferred flags -> the deferred output positions
 //   k_samtext_head     a lane per line: the same sam_text with an output pointer writes fields 1-9
 //                      and the tags at line_off, four bytes per store (SamOut)
 //   k_samtext_bulk     SEQ \t QUAL, about two thirds of the text, the way k_sam_bulk moves it the
-//                      other way: a wave takes a tile of 64 lines, cuts each line's region into
-//                      16-byte units aligned in the OUTPUT, numbers the units with a wave scan and
-//                      gives them to consecutive lanes, so a wave store covers 1 KiB of consecutive
-//                      text and a 6 KB long read is the whole wave's work.  A unit's bytes come from
-//                      the packed nibbles or from the quality bytes + 33; the units at a region's
-//                      ends are partial.  A quality byte above 93 stops the output at that line.
+//                      other way (unit_tiles.h): each line's region is cut into 16-byte units aligned
+//                      in the OUTPUT.  A unit's bytes come from the packed nibbles or from the
+//                      quality bytes + 33; the units at a region's ends are partial.  A quality
+//                      byte above 93 stops the output at that line.
 //
 // Loads past a record stay inside the 64 readable bytes behind the records (include/hbam.h).
 
@@ -56,13 +54,6 @@ __global__ __launch_bounds__(SAMTEXT_WG) void k_samtext_sizes(const uint8_t* __r
   if (r.status != HBAM_OK) atomicMin(first_stop, (unsigned long long)k);
 }
 
-__global__ __launch_bounds__(SAMTEXT_WG) void k_samtext_deferred(const uint32_t* __restrict__ dflag,
-                                                                 const uint64_t* __restrict__ dpos, uint32_t n,
-                                                                 uint32_t* __restrict__ deferred) {
-  const uint32_t k = blockIdx.x * SAMTEXT_WG + threadIdx.x;
-  if (k < n && dflag[k]) deferred[dpos[k]] = k;
-}
-
 __global__ __launch_bounds__(SAMTEXT_WG) void k_samtext_head(const uint8_t* __restrict__ ub,
                                                              const uint64_t* __restrict__ rec_off,
                                                              const uint32_t* __restrict__ perm, uint32_t n,
@@ -85,69 +76,52 @@ __global__ __launch_bounds__(SAMTEXT_WG) void k_samtext_bulk(const uint8_t* __re
                                                              const uint64_t* __restrict__ line_off, uint32_t n,
                                                              uint8_t* __restrict__ text, int32_t* __restrict__ status,
                                                              unsigned long long* first_stop) {
-  __shared__ uint32_t s_excl[SAMTEXT_WG / 64][64];
   __shared__ uint4 s_desc[SAMTEXT_WG / 64][64];
   __shared__ uint2 s_reg[SAMTEXT_WG / 64][64];
-  const uint32_t lane = threadIdx.x & 63u;
-  uint32_t* const ex = s_excl[threadIdx.x >> 6];
   uint4* const sd = s_desc[threadIdx.x >> 6];
   uint2* const sr = s_reg[threadIdx.x >> 6];
-  const uint32_t ntiles = (n + 63u) / 64u;
-  const uint32_t wstride = gridDim.x * (SAMTEXT_WG / 64);
-  for (uint32_t t = blockIdx.x * (SAMTEXT_WG / 64) + (threadIdx.x >> 6); t < ntiles; t += wstride) {
-    const uint32_t line = t * 64u + lane;
-    uint4 d = make_uint4(0, SAMTEXT_NONE, 0, 0);
-    uint64_t R = 0;
-    uint32_t blen = 0;
-    if (line < n) {
-      d = desc[line];
-      if (d.y != SAMTEXT_NONE) {
-        const uint32_t ls = d.x & 0x7fffffffu;
-        R = d.y == SAMTEXT_CHECK ? 0 : line_off[line] + d.y;
-        blen = ls + 1u + ((d.x >> 31) ? 1u : ls);
-      }
-    }
-    const uint32_t units = sam_text_units(R, blen);
-    const uint32_t incl = wave_scan_dpp(units), T = wave_last(incl);
-    if (T == 0u) continue;  // wave-uniform
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");  // the previous tile's reads of ex / sd / sr precede these writes
-    ex[lane] = incl - units;
-    sd[lane] = d;
-    sr[lane] = make_uint2((uint32_t)R, (uint32_t)(R >> 32));
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");  // (one wave: its LDS operations run in issue order)
-    for (uint32_t q0 = 0; q0 < T; q0 += 64u) {
-      const uint32_t q = q0 + lane;
-      if (q >= T) continue;
-      // the last line whose first unit is <= q (ex[0] = 0; lines without units tie with the next one)
-      uint32_t r = 0, hi = 63;
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        const uint32_t mid = (r + hi + 1u) >> 1;
-        if (ex[mid] <= q) r = mid;
-        else hi = mid - 1u;
-      }
-      const uint4 D = sd[r];
-      const uint2 RR = sr[r];
-      const uint64_t Rr = (uint64_t)RR.x | (uint64_t)RR.y << 32;
-      const uint32_t ls = D.x & 0x7fffffffu, star = D.x >> 31;
-      uint32_t p0, nb, o[4];
-      sam_text_unit_span(Rr, ls + 1u + (star ? 1u : ls), q - ex[r], &p0, &nb);
-      const bool ok = sam_text_unit(ub + ((uint64_t)D.z | (uint64_t)D.w << 32), ls, star, p0, nb, o);
-      const u32x4_a1 v = u32x4_a1{o[0], o[1], o[2], o[3]};
-      HBAM_G uint8_t* const gd = (HBAM_G uint8_t*)(text + Rr + p0);
-      if (D.y != SAMTEXT_CHECK) {
-        if (nb >= 16u) *(HBAM_G u32x4_a1*)gd = v;
-        else st_part_g(gd, nb, v);
-      }
-      if (!ok) {
-        const uint32_t bad = t * 64u + r;
-        status[bad] = HBAM_EREFID;
-        atomicMin(first_stop, (unsigned long long)bad);
-      }
-    }
-  }
+  uint4 d;
+  uint64_t R;
+  unit_tiles<SAMTEXT_WG>(
+      n,
+      [&](uint32_t line) {
+        d = make_uint4(0, SAMTEXT_NONE, 0, 0);
+        R = 0;
+        uint32_t blen = 0;
+        if (line < n) {
+          d = desc[line];
+          if (d.y != SAMTEXT_NONE) {
+            const uint32_t ls = d.x & 0x7fffffffu;
+            R = d.y == SAMTEXT_CHECK ? 0 : line_off[line] + d.y;
+            blen = ls + 1u + ((d.x >> 31) ? 1u : ls);
+          }
+        }
+        return sam_text_units(R, blen);
+      },
+      [&](uint32_t lane) {
+        sd[lane] = d;
+        sr[lane] = make_uint2((uint32_t)R, (uint32_t)(R >> 32));
+      },
+      [&](uint32_t t, uint32_t r, uint32_t k) {
+        const uint4 D = sd[r];
+        const uint2 RR = sr[r];
+        const uint64_t Rr = (uint64_t)RR.x | (uint64_t)RR.y << 32;
+        const uint32_t ls = D.x & 0x7fffffffu, star = D.x >> 31;
+        uint32_t p0, nb, o[4];
+        sam_text_unit_span(Rr, ls + 1u + (star ? 1u : ls), k, &p0, &nb);
+        const bool ok = sam_text_unit(ub + ((uint64_t)D.z | (uint64_t)D.w << 32), ls, star, p0, nb, o);
+        const u32x4_a1 v = u32x4_a1{o[0], o[1], o[2], o[3]};
+        HBAM_G uint8_t* const gd = (HBAM_G uint8_t*)(text + Rr + p0);
+        if (D.y != SAMTEXT_CHECK) {
+          if (nb >= 16u) *(HBAM_G u32x4_a1*)gd = v;
+          else st_part_g(gd, nb, v);
+        }
+        if (!ok) {
+          const uint32_t bad = t * 64u + r;
+          status[bad] = HBAM_EREFID;
+          atomicMin(first_stop, (unsigned long long)bad);
+        }
+      });
 }
 
 }  // namespace hbam
@@ -178,81 +152,39 @@ extern "C" int hbam_sam_render(hbam_ctx* c, const uint8_t* ubuf, const uint64_t*
   if (!on_device && n) {
     for (uint64_t i = 0; i < n; ++i)
       if (rec_off[i + 1] < rec_off[i]) return set_err(c, HBAM_EINVAL, "hbam_sam_render: rec_off must ascend");
-    const uint64_t bytes = rec_off[n];
-    uint8_t* dub;
-    uint64_t* dro;
-    if ((rc = ensure(c, B_ST_UBUF, bytes + 64, &dub)) || (rc = ensure(c, B_ST_RECOFF, n + 1, &dro))) return rc;
-    if (bytes) HIPCHK(c, hipMemcpyAsync(dub, ubuf, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(dub + bytes, 0, 64, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dro, rec_off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    ub = dub;
-    ro = dro;
+    // n + 1 offsets: k_samtext_* take a record's length from rec_off[i + 1]
+    if ((rc = stage_records(c, B_ST_UBUF, B_ST_RECOFF, ubuf, rec_off[n], rec_off, n + 1, &ub, &ro))) return rc;
   }
-  uint32_t *len, *dflag, *deferred;
-  int32_t* lstatus;
+  TextOut T{{B_ST_LEN, B_ST_STATUS, B_ST_LINEOFF, B_ST_SMALL, B_ST_TEXT, true, B_ST_DFLAG, B_ST_DPOS, B_ST_DEFERRED}};
   uint4* desc;
-  uint64_t *line_off, *dpos, *small;
-  if ((rc = ensure(c, B_ST_LEN, n + 1, &len)) || (rc = ensure(c, B_ST_STATUS, n + 1, &lstatus)) ||
-      (rc = ensure(c, B_ST_DFLAG, n + 1, &dflag)) || (rc = ensure(c, B_ST_DESC, n + 1, &desc)) ||
-      (rc = ensure(c, B_ST_LINEOFF, n + 1, &line_off)) || (rc = ensure(c, B_ST_DPOS, n + 1, &dpos)) ||
-      (rc = ensure(c, B_ST_DEFERRED, n + 1, &deferred)) || (rc = ensure(c, B_ST_SMALL, 2, &small)))
-    return rc;
-  unsigned long long* first_stop = (unsigned long long*)small;
-  HIPCHK(c, hipMemsetAsync(small, 0xff, 8, c->stream));
-  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+  if ((rc = ensure(c, B_ST_DESC, n + 1, &desc)) || (rc = textout_begin(c, n, &T))) return rc;
   if (n)
     k_samtext_sizes<<<grid_for(n, SAMTEXT_WG), SAMTEXT_WG, 0, c->stream>>>(ub, ro, perm, (uint32_t)n, dnames,
-                                                                          dname_off, n_ref, len, lstatus, dflag,
-                                                                          desc, first_stop);
+                                                                          dname_off, n_ref, T.len, T.lstatus, T.dflag,
+                                                                          desc, T.first_stop);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->pinned_small + 8, small, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  uint64_t m = n;  // the lines that stand
-  int32_t status = HBAM_OK;
-  if (c->pinned_small[8] < n) {
-    m = c->pinned_small[8];
-    HIPCHK(c, copy_sync(c, &status, lstatus + m, 4, hipMemcpyDeviceToHost));
-  }
-  uint64_t text_len = 0, n_def = 0;
-  if ((rc = scan_exclusive<uint32_t>(c, len, m, line_off, &text_len))) return rc;
-  if ((rc = scan_exclusive<uint32_t>(c, dflag, m, dpos, &n_def))) return rc;
-  if (m) k_samtext_deferred<<<grid_for(m, SAMTEXT_WG), SAMTEXT_WG, 0, c->stream>>>(dflag, dpos, (uint32_t)m, deferred);
-  HIPCHK(c, hipGetLastError());
-  uint8_t* text;
-  if ((rc = ensure(c, B_ST_TEXT, text_len + 64, &text))) return rc;
-  HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-  if (m)
-    k_samtext_head<<<grid_for(m, SAMTEXT_WG), SAMTEXT_WG, 0, c->stream>>>(ub, ro, perm, (uint32_t)m, dnames,
-                                                                         dname_off, n_ref, line_off, text);
+  if ((rc = textout_stop(c, &T))) return rc;
+  if (T.cut) HIPCHK(c, copy_sync(c, &T.status, T.lstatus + T.m, 4, hipMemcpyDeviceToHost));
+  if ((rc = textout_layout(c, &T))) return rc;
+  if (T.m)
+    k_samtext_head<<<grid_for(T.m, SAMTEXT_WG), SAMTEXT_WG, 0, c->stream>>>(ub, ro, perm, (uint32_t)T.m, dnames,
+                                                                           dname_off, n_ref, T.line_off, T.text);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-  HIPCHK(c, hipMemsetAsync(small, 0xff, 8, c->stream));
-  if (m)
-    k_samtext_bulk<<<(uint32_t)std::min<uint64_t>(grid_for(m, SAMTEXT_WG), POOLS_MAX_WG), SAMTEXT_WG, 0,
-                     c->stream>>>(ub, desc, line_off, (uint32_t)m, text, lstatus, first_stop);
+  if ((rc = textout_arm(c, T))) return rc;
+  if (T.m)
+    k_samtext_bulk<<<(uint32_t)std::min<uint64_t>(grid_for(T.m, SAMTEXT_WG), POOLS_MAX_WG), SAMTEXT_WG, 0,
+                     c->stream>>>(ub, desc, T.line_off, (uint32_t)T.m, T.text, T.lstatus, T.first_stop);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->pinned_small + 8, small, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->pinned_small[8] < m) {  // a quality byte: the lines before that record stand
-    m = c->pinned_small[8];
-    HIPCHK(c, copy_sync(c, &status, lstatus + m, 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, copy_sync(c, &text_len, line_off + m, 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, copy_sync(c, &n_def, dpos + m, 8, hipMemcpyDeviceToHost));
+  if ((rc = textout_stop(c, &T))) return rc;
+  if (T.cut) {  // a quality byte: the lines before that record stand, and the deferred ones among them
+    HIPCHK(c, copy_sync(c, &T.status, T.lstatus + T.m, 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, copy_sync(c, &T.text_len, T.line_off + T.m, 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, copy_sync(c, &T.n_def, T.dpos + T.m, 8, hipMemcpyDeviceToHost));
   }
-  out->n_records = m;
-  out->status = status;
-  out->err_record = status ? m : 0;
-  out->text_len = text_len;
-  out->text = text;
-  out->line_off = line_off;
-  out->n_deferred = n_def;
-  out->deferred = deferred;
-  c->timing.walk_ms = ev_ms(c, 0, 1);
-  c->timing.huffman_ms = ev_ms(c, 1, 2);
-  c->timing.resolve_ms = ev_ms(c, 2, 3);
-  c->timing.total_ms = ev_ms(c, 0, 3);
-  c->timing.n_records = m;
-  c->timing.ubuf_bytes = text_len;
+  textout_finish(c, T, out);
+  out->n_deferred = T.n_def;
+  out->deferred = T.deferred;
   return HBAM_OK;
 }

@@ -1,6 +1,6 @@
 // hbam_vcftext.hip — VCF text out of the device: htsjdk's VCFEncoder over BCF2 records
-// (VCFRecordWriter, the VCF half of VCFSort over a BCF input), the design of hbam_samtext.hip.
-// Included at the end of hbam_capi.hip.  gfx950, wave64.
+// (VCFRecordWriter, the VCF half of VCFSort over a BCF input), over the host sequence of
+// hbam_textout.hip.  Included at the end of hbam_capi.hip.  gfx950, wave64.
 //
 //   k_vcftext_sizes    a lane per output line: the record rendered by vcf_text (vcf_text.h) in its
 //                      counting mode for the line's length, its status and whether the host has to
@@ -11,8 +11,7 @@
 //                      lanes' findings are OR-ed through the wave), the key order is then computed
 //                      once, and each lane counts its samples' columns; a wave scan of the lengths
 //                      per 64 samples gives every column's offset.
-//   (scan_exclusive)   lengths -> line_off; deferred flags -> their ranks, k_samtext_deferred
-//                      compacts the deferred output positions, ascending
+//   (textout_layout)   lengths -> line_off; deferred flags -> the deferred output positions
 //   k_vcftext_write    a lane per line: the same vcf_text with an output pointer, four bytes per
 //                      store (SamOut); a marked line's site columns only
 //   k_vcftext_geno     (write) the same wave pass with an output pointer: lane 0 writes the FORMAT
@@ -239,76 +238,39 @@ extern "C" int hbam_vcf_render(hbam_ctx* c, const uint8_t* data, uint64_t data_l
   M.n_sample = hdr->n_sample;
   const uint8_t* ub = data;
   const uint64_t* ro = rec_off;
-  if (!on_device && n) {
-    uint8_t* dub;
-    uint64_t* dro;
-    if ((rc = ensure(c, B_VT_DATA, data_len + 64, &dub)) || (rc = ensure(c, B_VT_RECOFF, n + 1, &dro))) return rc;
-    if (data_len) HIPCHK(c, hipMemcpyAsync(dub, data, data_len, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(dub + data_len, 0, 64, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dro, rec_off, n * 8, hipMemcpyHostToDevice, c->stream));
-    ub = dub;
-    ro = dro;
-  }
-  uint32_t *len, *dflag, *deferred, *site;
-  int32_t* lstatus;
-  uint64_t *line_off, *dpos, *small;
-  if ((rc = ensure(c, B_VT_LEN, n + 1, &len)) || (rc = ensure(c, B_VT_STATUS, n + 1, &lstatus)) ||
-      (rc = ensure(c, B_VT_DFLAG, n + 1, &dflag)) || (rc = ensure(c, B_VT_SITE, n + 1, &site)) ||
-      (rc = ensure(c, B_VT_LINEOFF, n + 1, &line_off)) || (rc = ensure(c, B_VT_DPOS, n + 1, &dpos)) ||
-      (rc = ensure(c, B_VT_DEFERRED, n + 1, &deferred)) || (rc = ensure(c, B_VT_SMALL, 2, &small)))
+  // n offsets: a BCF record carries its own length, and k_vcftext_* never read rec_off[i + 1]
+  if (!on_device && n && (rc = stage_records(c, B_VT_DATA, B_VT_RECOFF, data, data_len, rec_off, n, &ub, &ro)))
     return rc;
-  unsigned long long* first_stop = (unsigned long long*)small;
-  HIPCHK(c, hipMemsetAsync(small, 0xff, 8, c->stream));
-  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+  TextOut T{{B_VT_LEN, B_VT_STATUS, B_VT_LINEOFF, B_VT_SMALL, B_VT_TEXT, true, B_VT_DFLAG, B_VT_DPOS, B_VT_DEFERRED}};
+  uint32_t* site;
+  if ((rc = ensure(c, B_VT_SITE, n + 1, &site)) || (rc = textout_begin(c, n, &T))) return rc;
   const bool waves = (uint32_t)hdr->n_sample >= HBAM_VCF_WAVE_SAMPLES;  // (a record's count must be the header's)
   if (n) {
     k_vcftext_sizes<<<grid_for(n, VCFTEXT_WG), VCFTEXT_WG, 0, c->stream>>>(ub, data_len, ro, perm, (uint32_t)n, M,
-                                                                          len, lstatus, dflag, site, first_stop);
+                                                                          T.len, T.lstatus, T.dflag, site,
+                                                                          T.first_stop);
     if (waves)
       k_vcftext_geno<<<grid_for(n, VCFTEXT_WG / 64), VCFTEXT_WG, 0, c->stream>>>(
-          ub, data_len, ro, perm, (uint32_t)n, M, site, len, lstatus, dflag, nullptr, nullptr, first_stop);
+          ub, data_len, ro, perm, (uint32_t)n, M, site, T.len, T.lstatus, T.dflag, nullptr, nullptr, T.first_stop);
   }
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->pinned_small + 8, small, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  uint64_t m = n;  // the lines that stand
-  int32_t status = HBAM_OK;
-  if (c->pinned_small[8] < n) {
-    m = c->pinned_small[8];
-    HIPCHK(c, copy_sync(c, &status, lstatus + m, 4, hipMemcpyDeviceToHost));
-  }
-  uint64_t text_len = 0, n_def = 0;
-  if ((rc = scan_exclusive<uint32_t>(c, len, m, line_off, &text_len))) return rc;
-  if ((rc = scan_exclusive<uint32_t>(c, dflag, m, dpos, &n_def))) return rc;
-  if (m) k_samtext_deferred<<<grid_for(m, SAMTEXT_WG), SAMTEXT_WG, 0, c->stream>>>(dflag, dpos, (uint32_t)m, deferred);
-  HIPCHK(c, hipGetLastError());
-  uint8_t* text;
-  if ((rc = ensure(c, B_VT_TEXT, text_len + 64, &text))) return rc;
-  HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-  if (m)
-    k_vcftext_write<<<grid_for(m, VCFTEXT_WG), VCFTEXT_WG, 0, c->stream>>>(ub, data_len, ro, perm, (uint32_t)m, M,
-                                                                          line_off, text);
+  if ((rc = textout_stop(c, &T))) return rc;
+  if (T.cut) HIPCHK(c, copy_sync(c, &T.status, T.lstatus + T.m, 4, hipMemcpyDeviceToHost));
+  if ((rc = textout_layout(c, &T))) return rc;
+  if (T.m)
+    k_vcftext_write<<<grid_for(T.m, VCFTEXT_WG), VCFTEXT_WG, 0, c->stream>>>(ub, data_len, ro, perm, (uint32_t)T.m, M,
+                                                                            T.line_off, T.text);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-  if (m && waves)
-    k_vcftext_geno<<<grid_for(m, VCFTEXT_WG / 64), VCFTEXT_WG, 0, c->stream>>>(
-        ub, data_len, ro, perm, (uint32_t)m, M, site, len, lstatus, dflag, line_off, text, first_stop);
+  if (T.m && waves)
+    k_vcftext_geno<<<grid_for(T.m, VCFTEXT_WG / 64), VCFTEXT_WG, 0, c->stream>>>(
+        ub, data_len, ro, perm, (uint32_t)T.m, M, site, T.len, T.lstatus, T.dflag, T.line_off, T.text, T.first_stop);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+  // no second stop: every check ran in the sizes passes, and the write passes do not touch first_stop
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  out->n_records = m;
-  out->status = status;
-  out->err_record = status ? m : 0;
-  out->text_len = text_len;
-  out->text = text;
-  out->line_off = line_off;
-  out->n_deferred = n_def;
-  out->deferred = deferred;
-  c->timing.walk_ms = ev_ms(c, 0, 1);
-  c->timing.huffman_ms = ev_ms(c, 1, 2);
-  c->timing.resolve_ms = ev_ms(c, 2, 3);
-  c->timing.total_ms = ev_ms(c, 0, 3);
-  c->timing.n_records = m;
-  c->timing.ubuf_bytes = text_len;
+  textout_finish(c, T, out);
+  out->n_deferred = T.n_def;
+  out->deferred = T.deferred;
   return HBAM_OK;
 }

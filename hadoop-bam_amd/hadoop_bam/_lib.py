@@ -1017,6 +1017,25 @@ class Context:
             return int(r), None
         return 0, out[:r]
 
+    @staticmethod
+    def _devptr(x):
+        """A device pointer given as an int, None, a ctypes pointer or a torch tensor -> c_void_p."""
+        if hasattr(x, "data_ptr"):
+            import torch
+            torch.cuda.current_stream(x.device).synchronize()
+            return C.c_void_p(x.data_ptr())
+        return C.c_void_p(x) if isinstance(x, (int, type(None))) else C.cast(x, C.c_void_p)
+
+    def _text_result(self, rc, t):
+        """A render's (rc, SamTextC) -> the dict of sam_render and vcf_render."""
+        if rc:
+            return {"rc": rc, "error": self.last_error()}
+        k = int(t.n_records)
+        return {"rc": 0, "n": k, "status": int(t.status), "err_record": int(t.err_record),
+                "text": self._d2h(t.text, int(t.text_len), np.uint8).tobytes(),
+                "line_off": self._d2h(t.line_off, k + 1, np.uint64),
+                "deferred": self._d2h(t.deferred, int(t.n_deferred), np.uint32), "timing": self.timing()}
+
     # ---- read-name / CIGAR keyed consumers (SURVEY.md §8 f-4) --------------------------------
     def _d2h(self, ptr, n, dtype):
         """Copy n elements of a device array (context-owned) to a numpy array."""
@@ -1423,16 +1442,9 @@ class Context:
         if n is None:
             n = int(cols.n)
         wp, wn, wdev, wkeep = self._ptr(window)
-        if perm is not None and hasattr(perm, "data_ptr"):
-            import torch
-            torch.cuda.current_stream(perm.device).synchronize()
-            perm_p = C.c_void_p(perm.data_ptr())
-        else:
-            perm_p = perm if isinstance(perm, (C.c_void_p, type(None))) else C.c_void_p(
-                perm if isinstance(perm, int) else C.cast(perm, C.c_void_p).value)
         t = FragTextC()
-        rc = self.L.hbam_frag_render(self.h, C.byref(cols), wp, wdev, wn, perm_p, int(n), int(fmt), int(encoding),
-                                     int(flags), C.byref(t))
+        rc = self.L.hbam_frag_render(self.h, C.byref(cols), wp, wdev, wn, self._devptr(perm), int(n), int(fmt),
+                                     int(encoding), int(flags), C.byref(t))
         del keep, wkeep
         return rc, t
 
@@ -1492,7 +1504,7 @@ class Context:
         t = SamTextC()
         vp = C.c_void_p
         if on_device:
-            args = [C.cast(x, vp) if not isinstance(x, (int, type(None))) else vp(x) for x in (ubuf, rec_off, perm)]
+            args = [self._devptr(x) for x in (ubuf, rec_off, perm)]
             keep = None
         else:
             if perm is not None:
@@ -1514,14 +1526,7 @@ class Context:
         """hbam_sam_render and a host copy of what it wrote -> dict: n, status, err_record, text
         (bytes; a deferred line is empty), line_off (uint64[n + 1]), deferred (uint32, ascending
         output positions), timing."""
-        rc, t = self.sam_render_device(ubuf, rec_off, n, names, perm, on_device)
-        if rc:
-            return {"rc": rc, "error": self.last_error()}
-        k = int(t.n_records)
-        return {"rc": 0, "n": k, "status": int(t.status), "err_record": int(t.err_record),
-                "text": self._d2h(t.text, int(t.text_len), np.uint8).tobytes(),
-                "line_off": self._d2h(t.line_off, k + 1, np.uint64),
-                "deferred": self._d2h(t.deferred, int(t.n_deferred), np.uint32), "timing": self.timing()}
+        return self._text_result(*self.sam_render_device(ubuf, rec_off, n, names, perm, on_device))
 
     # ---- VCF text output (hbam_vcftext.hip) --------------------------------------------------------
     def bcf_header_text(self, file_prefix):
@@ -1566,7 +1571,7 @@ class Context:
         hc = self._bcf_hdr(dict(h, bgzf=0, header_len=0))
         t = SamTextC()
         if on_device:
-            args = [C.cast(x, vp) if not isinstance(x, (int, type(None))) else vp(x) for x in (data, rec_off, perm)]
+            args = [self._devptr(x) for x in (data, rec_off, perm)]
         else:
             if perm is not None:
                 raise ValueError("perm needs device arguments")
@@ -1586,14 +1591,7 @@ class Context:
         """hbam_vcf_render and a host copy of what it wrote -> dict: n, status, err_record, text
         (bytes; a deferred line is empty), line_off (uint64[n + 1]), deferred (uint32, ascending
         output positions), timing."""
-        rc, t = self.vcf_render_device(data, data_len, rec_off, n, h, meta, perm, on_device)
-        if rc:
-            return {"rc": rc, "error": self.last_error()}
-        k = int(t.n_records)
-        return {"rc": 0, "n": k, "status": int(t.status), "err_record": int(t.err_record),
-                "text": self._d2h(t.text, int(t.text_len), np.uint8).tobytes(),
-                "line_off": self._d2h(t.line_off, k + 1, np.uint64),
-                "deferred": self._d2h(t.deferred, int(t.n_deferred), np.uint32), "timing": self.timing()}
+        return self._text_result(*self.vcf_render_device(data, data_len, rec_off, n, h, meta, perm, on_device))
 
     def vcf_gather_lines(self, dcols, perm=None, n=None):
         """hbam_vcf_gather_lines over the device columns of a keep_text decode: lines perm[0..n)

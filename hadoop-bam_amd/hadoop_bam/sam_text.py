@@ -203,20 +203,25 @@ def render_record(record_bytes, names):
     return b"\t".join(cols) + b"\n"
 
 
+def spliced_pieces(res, render_at):
+    """The pieces of a render's host copy (Context.sam_render's or vcf_render's dict) in output
+    order: the device's text up to each deferred line, then render_at(k) for that line's output
+    position k, then the rest."""
+    text, lo, at = res["text"], res["line_off"], 0
+    for k in res["deferred"]:
+        cut = int(lo[int(k)])
+        yield text[at:cut]
+        yield render_at(int(k))
+        at = cut
+    yield text[at:]
+
+
 def splice(res, record_at, names):
     """The host copy of a render (Context.sam_render's dict) with its deferred lines filled in:
     record_at(k) = the bytes of the record of output position k."""
-    text, lo = res["text"], res["line_off"]
     if not len(res["deferred"]):
-        return text
-    out, at = [], 0
-    for k in res["deferred"]:
-        cut = int(lo[int(k)])
-        out.append(text[at:cut])
-        out.append(render_record(record_at(int(k)), names))
-        at = cut
-    out.append(text[at:])
-    return b"".join(out)
+        return res["text"]
+    return b"".join(spliced_pieces(res, lambda k: render_record(record_at(k), names)))
 
 
 def header_text(header):

@@ -16,6 +16,7 @@ import numpy as np
 from . import _lib
 from .bcf import BCFDecodeRuntimeException, TribbleException, read_bcf_header
 from .formats import Configuration, IllegalArgumentException, IOException, SeekableFile, context, raise_for
+from .sam_text import spliced_pieces
 from .vcf import VCFFormat, VCFRecord, read_vcf_header
 
 OUTPUT_VCF_FORMAT_PROPERTY = "hadoopbam.vcf.output-format"
@@ -522,13 +523,8 @@ class VCFRecordWriter:
         order ends the output, whether the device or the host renderer found it."""
         if res["rc"]:
             raise_for(res["rc"], res.get("error", ""))
-        text, lo, at = res["text"], res["line_off"], 0
-        for k in res["deferred"]:
-            cut = int(lo[int(k)])
-            self.orig.write(text[at:cut])
-            at = cut
-            self.orig.write(render_record(record_at(int(k)), self.header))
-        self.orig.write(text[at:])
+        for piece in spliced_pieces(res, lambda k: render_record(record_at(k), self.header)):
+            self.orig.write(piece)
         if res["status"] != _lib.HBAM_OK:
             _fail(res["status"], "record %d of the batch" % res["err_record"])
 

@@ -159,6 +159,35 @@ def stream(case_slot, at, total=130):
     return recs
 
 
+def deferred_record(k):
+    """good_record(k) with its NM tag replaced by a float outside the device's domain"""
+    return _reaux(good_record(k), 4, aux_f("XF", 0.5))
+
+
+def stop_streams():
+    """[(name, slots, n, status, deferred)]: 130 records with deferred ones at 3, 63 and 100, and one or
+    two failing records: a malformed tag (found when the lines are sized) and a quality byte of 94
+    (found when SEQ and QUAL are written).  The first failing record in output order ends the output,
+    and only the deferred records before it are listed."""
+    malformed = _with_aux(f4_records.aux_int("NM", "C", 7) + b"XY")
+    quality = _with_qual(17, 94)
+
+    def make(bad):
+        recs = [good_record(k) for k in range(130)]
+        for k in (3, 63, 100):
+            recs[k] = deferred_record(k)
+        for k, slot in bad.items():
+            recs[k] = slot
+        return recs
+    return [
+        ("malformed_64", make({64: malformed}), 64, E, [3, 63]),
+        ("quality_64", make({64: quality}), 64, R, [3, 63]),
+        ("quality_101", make({101: quality}), 101, R, [3, 63, 100]),
+        ("malformed_100_quality_40", make({100: malformed, 40: quality}), 40, R, [3]),
+        ("quality_120_malformed_100", make({120: quality, 100: malformed}), 100, E, [3, 63]),
+    ]
+
+
 def host_input(slots, names=NAMES):
     """The input file of tools/sam_text_host.cpp."""
     noff = np.zeros(len(names) + 1, np.uint32)

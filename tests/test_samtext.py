@@ -83,6 +83,17 @@ def test_device_record_rules_on_the_cpu_match_the_restatement(tmp_path):
     assert [ref.deferred(r) for r, _ in cases.float_records()] == [d for _, d in cases.float_records()]
 
 
+def test_restatement_stops_at_the_first_of_two_failing_records():
+    """The streams of test_samtext_gpu.test_stops_among_deferred_records: the restatement ends at the
+    first failing record in output order, whichever rule finds it, and lists the deferred records
+    before it."""
+    for name, slots, n, status, deferred in cases.stop_streams():
+        want = ref.render(slots, cases.NAMES)
+        assert (want["n"], want["status"], want["deferred"]) == (n, status, deferred), name
+        assert len(want["text"]) == int(want["line_off"][n]) and len(want["line_off"]) == n + 1, name
+        assert all(want["lines"][k] == b"" for k in deferred) and want["lines"][0] != b"", name
+
+
 def test_java_float_to_string_matches_the_restatement():
     from hadoop_bam import java_float_to_string
     for v, text in zip(FLOATS, FLOAT_TEXT):

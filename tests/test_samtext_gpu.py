@@ -144,6 +144,19 @@ def test_status_cases(gpu_ctx, case):
         same(render_host(gpu_ctx, slots), want, (name, at))
 
 
+@pytest.mark.parametrize("case", cases.stop_streams(), ids=[c[0] for c in cases.stop_streams()])
+def test_stops_among_deferred_records(gpu_ctx, case):
+    """A stop found by the sizes pass, by the bulk pass, or by both in one stream, with deferred records
+    before and behind it: the first failing record in output order ends the output, the deferred list
+    holds the positions before it, and text_len is the offset of that record's line."""
+    name, slots, n, status, deferred = case
+    want = ref.render(slots, cases.NAMES)
+    assert (want["n"], want["status"], want["deferred"]) == (n, status, deferred)
+    got = render_host(gpu_ctx, slots)
+    same(got, want, name)
+    assert len(got["text"]) == int(got["line_off"][n])
+
+
 @pytest.mark.parametrize("name", GOLDEN_BAMS)
 def test_sam_text_in_and_out_on_the_device(gpu_ctx, name):
     """SAM text -> hbam_sam_decode_split -> hbam_sam_render over the decode's device columns gives

@@ -104,6 +104,14 @@ def test_restatement_partial_and_status_rules():
     both = cases.with_qual_byte(cases.with_qual_byte(recs, 1, 0, 100), 1, -1, 0x80)
     assert ref.render(both, "qseq", True)["status"] == ref.EUNSUPPORTED
     assert ref.render(cases.with_qual_byte(recs, 0, 0, 0x20), "qseq", True)["status"] == 0
+    # two failing records in one stream: the first in output order ends it
+    two = cases.with_qual_byte(cases.with_qual_byte(recs, 3, 0, 127), 1, -1, 32)
+    got = ref.render(two, "fastq", True, True)
+    assert (got["status"], got["err_record"], got["n"], len(got["line_off"])) == (ref.ESEQFORMAT, 1, 1, 2)
+    assert got["text"] == ref.render(two[:1], "fastq", True, True)["text"]
+    two = cases.with_qual_byte(cases.with_qual_byte(recs, 3, 0, 0x80), 1, -1, 96)
+    got = ref.render(two, "qseq", True)
+    assert (got["status"], got["err_record"], got["n"]) == (ref.ERUNTIME, 1, 1)
 
 
 @pytest.fixture(scope="module")

@@ -338,6 +338,58 @@ def test_perm_on_device_columns(gpu_ctx):
     assert got["text"] == want["text"]
 
 
+def device_columns(ctx, c):
+    """cases.columns' host arrays uploaded -> (a device FragColumnsC, the buffers to free)."""
+    from hadoop_bam._lib import FragColumnsC
+    d, bufs = FragColumnsC(), []
+    d.n, d.host = c["n"], 0
+
+    def up(name, a):
+        bufs.append(ctx.upload(np.ascontiguousarray(a).tobytes() + bytes(16)))
+        setattr(d, name, bufs[-1].ptr)
+    for k in ("present",) + cases.INT_COLS + cases.STR_COLS:
+        up(k, c[k])
+    for k in ("key", "seq", "qual"):
+        up(k + "_off", c[k + "_off"])
+        up(k, c[k])
+        setattr(d, k + "_len", len(c[k]))
+    return d, bufs
+
+
+@pytest.mark.parametrize("fmt", ["fastq", "qseq"])
+def test_a_bad_index_and_a_bad_quality_byte_in_one_call(gpu_ctx, shorts, fmt):
+    """130 output positions over device columns: an index outside the columns (the sizes pass's
+    HBAM_EINVAL) and a record with an illegal quality byte (the bulk pass), either one first.  The
+    first of the two in output order ends the output.  The restatement knows no index, so the
+    expectation is its render of the records before the bad index: with the quality byte among them it
+    stops there with the writer's exception and the partial record; with the byte behind the bad index
+    it renders them all, and the status is HBAM_EINVAL at that position."""
+    import torch
+    recs = cases.with_qual_byte(shorts, 7, -1, 127 if fmt == "fastq" else 96)
+    c = cases.columns(recs)
+    d, bufs = device_columns(gpu_ctx, c)
+    try:
+        for bad_index, bad_qual in ((100, 40), (40, 100)):
+            perm = [(3 * k) % 7 + 8 * (k % 8) + 8 for k in range(130)]  # never record 7
+            perm[bad_qual], perm[bad_index] = 7, len(recs)
+            assert max(perm[:bad_index] + perm[bad_index + 1:]) < len(recs) and perm.count(7) == 1
+            want = ref.render([recs[i] for i in perm[:bad_index]], fmt, True, True)
+            t = torch.tensor(perm, dtype=torch.int32, device="cuda")
+            got = gpu_ctx.frag_render(d, c["window"], len(perm), FMT[fmt], 1, cases.USE_KEY, perm=t)
+            if bad_qual < bad_index:
+                assert (want["status"], want["err_record"]) == (ref.ESEQFORMAT if fmt == "fastq" else ref.ERUNTIME, 40)
+                assert (len(want["partial"]) > 0) == (fmt == "fastq")
+                assert_render(got, want, (fmt, "quality first"))
+            else:
+                assert (want["status"], want["n"], len(want["line_off"])) == (0, 40, 41)
+                assert (got["rc"], got["status"], got["err_record"], got["n"]) == (0, EINVAL, 40, 40)
+                assert [int(x) for x in got["line_off"]] == want["line_off"]
+                assert (got["text"], got["partial"]) == (want["text"], b"")
+    finally:
+        for b in bufs:
+            b.free()
+
+
 # ---- 6. convert -----------------------------------------------------------------------------------------
 def generated_fastq(term, records=2000, seed=9):
     r = random.Random(seed)

@@ -119,6 +119,16 @@ def test_status_case(name):
 
 
 # ---- 4. output format classes --------------------------------------------------------------------------------
+def test_restatement_stops_at_the_first_of_two_failing_records():
+    """the streams of test_vcftext_gpu.test_stop_among_deferred_records: the first failing record ends the
+    output, the deferred records before it are listed, and the record behind it fails on its own"""
+    for name, e, recs, n, status, deferred in C.stop_streams():
+        got = R.render_stream(recs, e.hdr)
+        assert (got["n"], got["status"], got["deferred"]) == (n, status, deferred), name
+        assert len(got["text"]) == got["line_off"][n] and len(got["line_off"]) == n + 1, name
+        assert R.render(recs[90], e.hdr)[0] not in (R.OK, status) and R.render(recs[100], e.hdr)[2] is True, name
+
+
 def test_output_format_constructors():
     assert V.OUTPUT_VCF_FORMAT_PROPERTY == "hadoopbam.vcf.output-format"
     assert V.WRITE_HEADER_PROPERTY == "hadoopbam.vcf.write-header"

@@ -117,6 +117,17 @@ def test_status_cases(gpu_ctx, name, at):
     assert_same(render(gpu_ctx, STATUS_ENC, recs), ref)
 
 
+@pytest.mark.parametrize("case", C.stop_streams(), ids=[c[0] for c in C.stop_streams()])
+def test_stop_among_deferred_records(gpu_ctx, case):
+    """a failing record with deferred records before and behind it and another failing record behind
+    it, found by the lane pass (3 samples) and by the wave pass's sizes half (70 samples)"""
+    name, e, recs, n, status, deferred = case
+    ref = R.render_stream(recs, e.hdr)
+    assert (ref["n"], ref["status"], ref["deferred"]) == (n, status, deferred)
+    assert_same(render(gpu_ctx, e, recs), ref)
+    assert_same(render(gpu_ctx, e, recs, device=True), ref)
+
+
 # ---- end to end -----------------------------------------------------------------------------------------
 def decode_and_render(ctx, file_bytes):
     from hadoop_bam.vcf_text import read_vcf_header_from

@@ -337,6 +337,32 @@ def status_cases():
     ]
 
 
+def stop_streams():
+    """-> [(name, Enc, records, n, status, deferred)]: 130 records with deferred ones at 3, 63 and 100, a
+    failing record at 64 and another, of another status, at 90.  "lanes": three samples, a record of 17
+    genotype fields deferred; "waves": 70 samples, so the samples' checks and the deferral (a null
+    value under Number=G) are the wave pass's."""
+    extra = [("Y%02d" % i, "1", "Integer") for i in range(16)]
+    e = craft_encoder(extra_fmt=extra)
+    gt3 = ("GT", INT8, 2, [[2, 4], [2, 2], [4, 4]])
+    many = e.record(pos=7, fmt=[gt3] + [(n, INT8, 1, [[i], [i + 1], [i + 2]]) for i, (n, _, _) in enumerate(extra)])
+    lanes = varied_records(e, 130)
+    lanes[64] = e.record(fmt=[gt3, ("DP", INT8, 2, [[1, 2], [3, 4], [5, 6]])])  # status_cases' dp_vector
+    lanes[90] = e.record(info=[("NOLINE", ints([1]))], fmt=[gt3])               # ... and info_no_line
+    ns = 70
+    w = craft_encoder(samples=tuple("N%d" % i for i in range(ns)))
+    gt = [[2, 4]] * ns
+    ok = w.record(pos=1, fmt=[("GT", INT8, 2, gt), ("DP", INT8, 1, [[s % 100] for s in range(ns)])])
+    g_null = w.record(pos=4, fmt=[("GT", INT8, 2, gt),
+                                  ("XG", INT8, 3, [[1, 2, 3]] * 65 + [[MISS[INT8]] * 3] + [[4, 5, 6]] * 4)])
+    waves = [ok] * 130
+    waves[64] = w.record(pos=2, fmt=[("GT", INT8, 2, gt[:68] + [[2, 8]] + gt[69:])])  # an allele the record lacks
+    waves[90] = w.record(pos=3, fmt=[("DP", INT8, 2, [[1, 2]] * ns)])
+    for k in (3, 63, 100):
+        lanes[k], waves[k] = many, g_null
+    return [("lanes", e, lanes, 64, R.EUNSUPPORTED, [3, 63]), ("waves", w, waves, 64, R.ERUNTIME, [3, 63])]
+
+
 def sample_records(n_sample, n_rec=8, seed=3):
     """Records of n_sample samples with GT, DP, one Number=2 generic field and ragged trailing-missing
     samples; nothing in them is deferred -> (Enc, [record])."""
